@@ -8,7 +8,9 @@ polynomial of degree 2^24 per GPU, hiding off -- the shape bench-templates times
     open   : witness polynomial p/(x-z) on the device          (kzg10/mod.rs:217-240)
              MSM of d pairs                                    (kzg10/mod.rs:255-258)
 SRS, coefficients and the quotient stay in HBM; only the two 96-byte affine results come back.  value = G1 (base,
-scalar) pairs per second, whole job.  The same JSON line carries, timed in the same run:
+scalar) pairs per second, whole job.  A plain run does that and nothing else: set-up, --warmup steps, --steps timed steps,
+the last step's commitment and proof written by --dump-outputs DIR, the line.  With --full the same JSON line carries, timed
+in the same run:
     secondary            the 2^20 case (BASELINE configs[1])
     trait_shaped         the same commit+open through BLOCKING calls with HOST coefficients (what the trait's
                          commit(&poly)/open(&poly) hands over) at 2^24 and 2^20
@@ -19,7 +21,7 @@ scalar) pairs per second, whole job.  The same JSON line carries, timed in the s
     roofline, cpu_baseline, parity
 
 Every workload runs on a TRUE structured reference string beta^i g generated on the device, so that its results are
-checked in-line against closed forms (C = p(beta) g, W = q(beta) g -- the verifier's pairing equation with the
+checked in-line (--full) against closed forms (C = p(beta) g, W = q(beta) g -- the verifier's pairing equation with the
 trapdoor known) evaluated by the CPU oracle: `parity` in the line says what was compared.
 
 N > 1 (`--gpus N`: this script launches its own ranks with torch.distributed.run when WORLD_SIZE is not set; the
@@ -334,9 +336,17 @@ def from_mont_limbs(curve, limbs):
 
 
 def seed_fr(curve, seed):
-    """One reproducible field element as a Python int (the oracle's SplitMix64 stream)."""
+    """One reproducible field element as a Python int (the oracle's SplitMix64 stream, restated in oracle/pyref.py: no native
+    oracle is loaded, so a plain run reads nothing of the oracle's build and writes nothing next to it)."""
+    import pyref
+    return pyref.gen_scalars(pyref.CURVES[curve]["fr"], seed, 1)[0] % fr_modulus(curve)
+
+
+def generator_xy(curve):
+    """The curve's generator as the device reads an affine point: x, y in Montgomery form (= oracle_lib.gen_bases(curve, 1)[0])."""
     import oracle_lib as O
-    return int.from_bytes(O.gen_scalars(curve, seed, 1).tobytes(), "little") % fr_modulus(curve)
+    import pyref
+    return O.points_to_array(curve, [pyref.generator(curve)])[0]
 
 
 def rand_fr_device(seed, n):
@@ -700,11 +710,10 @@ class KzgSetup:
 
     def __init__(self, ctx, D, args, curve, n, seed):
         import torch
-        import oracle_lib as O
         from poly_commit_amd import sharded
         self.ctx, self.D, self.curve, self.n = ctx, D, curve, n
         self.p = fr_modulus(curve)
-        self.g = O.gen_bases(curve, 1)[0]
+        self.g = generator_xy(curve)
         self.beta = seed_fr(curve, 0xBE7A24)
         self.z = seed_fr(curve, 0x2EE7)
         self.eng = sharded.HipEngine(ctx, curve)
@@ -746,8 +755,9 @@ class KzgSetup:
         torch.cuda.empty_cache()
 
 
-def kzg_case(ctx, D, args, curve, log_degree, steps, warmup, with_h2d, seed=0x5EED0001):
-    """One KZG commit+open workload on this rank.  Returns a dict (timings are the max over ranks)."""
+def kzg_case(ctx, D, args, curve, log_degree, steps, warmup, with_h2d, seed=0x5EED0001, full=True):
+    """One KZG commit+open workload on this rank.  Returns a dict (timings are the max over ranks).  full=False: the timed steps
+    and the last step's outputs only -- no parity check, no host-coefficient / trait-shaped legs, no roofline or phase figures."""
     import collections
     import torch
     world, rank, dist = D.world, D.rank, D.dist
@@ -824,6 +834,25 @@ def kzg_case(ctx, D, args, curve, log_degree, steps, warmup, with_h2d, seed=0x5E
         steps = max(10, int(math.ceil(1.2 / max(est, 1e-4))))
     dt, per_rank_dt, phases, marks = timed(step_resident, steps, warmup)
     timed_results = list(results)
+    # what the caller of the last timed step received: its commitment and its proof
+    last = {"commitment": [pt for k, pt in timed_results if k == "commit"][-1],
+            "proof": [pt for k, pt in timed_results if k == "open"][-1]}
+    pairs_per_step = (2 * n - 1) if world == 1 else world * (2 * n) - 1
+    res = {
+        "log_degree": log_degree, "steps": steps, "warmup": warmup, "dt": dt, "pairs_per_step": pairs_per_step,
+        "value": pairs_per_step * steps / dt, "ms_per_step": dt / steps * 1e3,
+        "per_rank_ms_per_step": [x / steps * 1e3 for x in per_rank_dt],
+        "commit_open_per_s": steps / dt,
+        "value_h2d_inclusive": None, "trait_shaped": None, "parity": None,
+        "srs_gen_ms": S.srs_gen_ms, "srs_window_table_build_ms": eng.precompute_ms,
+        "exchange_host_ms": ({k: (v / max(1, job.exchange_ms["calls"]) if k != "calls" else v) for k, v in job.exchange_ms.items()}
+                             if dist is not None else None),
+        "blocking_msm_ms": None, "msm_phase_ms": None, "roofline": None,
+        "last_outputs": last,
+    }
+    if not full:
+        S.free()
+        return res
 
     # accumulate launches of the timed region: [marks[3], marks[4]] of every MSM of this rank.  Launches of different
     # pipelines overlap, so the per-launch duration the region sustains is the UNION of the intervals / launches
@@ -946,7 +975,6 @@ def kzg_case(ctx, D, args, curve, log_degree, steps, warmup, with_h2d, seed=0x5E
     if not in_region:           # --inflight 0 (blocking calls leave no per-launch marks): the serial figure stands in
         acc_union_ms = float(sp[3])
 
-    pairs_per_step = (2 * n - 1) if world == 1 else world * (2 * n) - 1
     acc_serial_ms = float(sp[3])
     launch_pairs = ((2 * n - 1) / 2.0 if world == 1 else n - 0.5 / world) if in_region else float(n)
     bytes_per_launch = launch_pairs * PAIR_BYTES[curve]
@@ -965,15 +993,8 @@ def kzg_case(ctx, D, args, curve, log_degree, steps, warmup, with_h2d, seed=0x5E
                  "note": "reported beside the prescribed HBM roofline: the kernel is modular arithmetic on the VALU; peak = a "
                          "memory-free loop of the same addition on this GPU (the builder's own micro-benchmark: a "
                          "self-referential bound; against the bare v_mad_u64_u32 issue rate the kernel is at ~53 %)"}
-    res = {
-        "log_degree": log_degree, "steps": steps, "warmup": warmup, "dt": dt, "pairs_per_step": pairs_per_step,
-        "value": pairs_per_step * steps / dt, "ms_per_step": dt / steps * 1e3,
-        "per_rank_ms_per_step": [x / steps * 1e3 for x in per_rank_dt],
-        "commit_open_per_s": steps / dt,
+    res.update({
         "value_h2d_inclusive": h2d, "trait_shaped": trait, "parity": parity,
-        "srs_gen_ms": S.srs_gen_ms, "srs_window_table_build_ms": eng.precompute_ms,
-        "exchange_host_ms": ({k: (v / max(1, job.exchange_ms["calls"]) if k != "calls" else v) for k, v in job.exchange_ms.items()}
-                             if dist is not None else None),
         "blocking_msm_ms": blocking_msm_ms,
         "msm_phase_ms": {k: float(v) for k, v in zip(
             ["digits_hist", "scan", "scatter_fine_sort", "accumulate", "seg_reduce", "bucket_reduce"], sp[:6])},
@@ -1000,9 +1021,19 @@ def kzg_case(ctx, D, args, curve, log_degree, steps, warmup, with_h2d, seed=0x5E
                                 "algorithmic_bytes_per_launch": n * PAIR_BYTES[curve],
                                 "note": "3 blocking commit MSMs after the timed region (no second pipeline sharing the SIMDs): the "
                                         "duration rocprofv3's per-kernel average of an --inflight 0 run reproduces"}},
-    }
+    })
     S.free()
     return res
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy for every array the last timed step returned.  A point's 64-bit words are stored as their
+    32-bit halves, least significant first, in float64 (which holds every such limb exactly)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        limbs = np.ascontiguousarray(a, dtype="<u8").reshape(-1).view("<u4")
+        np.save(os.path.join(dirname, name + ".npy"), limbs.astype(np.float64))
+    log(f"outputs of the last timed step written to {dirname}: {', '.join(sorted(arrays))}")
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -1667,11 +1698,19 @@ def main():
     ap.add_argument("--log-degree", type=int, default=24,
                     help="degree of the primary workload (default 2^24: the north-star size; BASELINE.json's metric is "
                          "quoted at 2^20 and 2^24 -- the other one is reported in the `secondary` block)")
-    ap.add_argument("--secondary-log-degree", type=int, default=20, help="0 = no secondary block")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure (KZG runs): in-line parity against the CPU oracle, roofline and MSM phase "
+                         "figures (blocking MSMs and the micro-benchmark after the timed region), the host-coefficient and trait-shaped legs, "
+                         "the secondary degree, the extra workloads and the CPU baseline.  Without it a run sets up, warms up, times "
+                         "--steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (KZG: "
+                         "commitment.npy and proof.npy, the affine points' 32-bit limbs, least significant first, as float64)")
+    ap.add_argument("--secondary-log-degree", type=int, default=20, help="0 = no secondary block (--full)")
     ap.add_argument("--curve", default="bls12_381")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-h2d", action="store_true", help="skip the host-coefficients (H2D-inclusive) leg")
-    ap.add_argument("--no-trait", action="store_true", help="skip the trait-shaped leg (profile runs: its half-size launches would enter the per-kernel averages)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-h2d", action="store_true", help="(--full) skip the host-coefficients (H2D-inclusive) leg")
+    ap.add_argument("--no-trait", action="store_true", help="(--full) skip the trait-shaped leg (profile runs: its half-size launches would enter the per-kernel averages)")
     ap.add_argument("--window-bits", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--inflight", type=int, default=2,
@@ -1679,7 +1718,7 @@ def main():
     ap.add_argument("--workload", default="kzg", choices=["kzg", "ntt", "batch"],
                     help="what `value` measures: kzg (default, BASELINE configs[1] / north star), ntt (configs[4]) or batch (configs[2])")
     ap.add_argument("--workloads", default=None,
-                    help="comma list of the extra blocks timed in the same run at N = 1 (latency,batch,ipa,ligero); "
+                    help="(--full) comma list of the extra blocks timed in the same run at N = 1 (latency,batch,ipa,ligero); "
                          "default: all for the default kzg run; 'none' disables")
     ap.add_argument("--small", action="store_true", help="scaled-down sizes for every block (tests on a shared box); says so in the line")
     ap.add_argument("--polys", type=int, default=64)
@@ -1696,6 +1735,10 @@ def main():
                     help="1 (default): build the SRS window table in HBM once after the upload "
                          "(pc_hip_srs_precompute; part of SRS residency, outside the timed region); 0: table-free MSM")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.mode != "ranks" or args.workload != "kzg"):
+        ap.error("--dump-outputs writes the outputs of the KZG commit+open path (--workload kzg, --mode ranks)")
     if args.mode == "group":
         r = group_case(args, args.curve, min(args.log_degree, 16) if args.small else args.log_degree, args.steps or 10, args.warmup)
         emit(r)
@@ -1751,18 +1794,22 @@ def main():
             raise SystemExit("parity check FAILED")
         return
 
+    full = args.full
     log_degree = min(args.log_degree, 16) if small else args.log_degree
     sec_log = args.secondary_log_degree if not small else (12 if args.secondary_log_degree else 0)
-    prim = kzg_case(ctx, D, args, curve, log_degree, args.steps, args.warmup, with_h2d=not args.no_h2d)
-    log(f"primary 2^{log_degree}: {prim['ms_per_step']:.2f} ms/step, parity {prim['parity']['commit_ok']}/{prim['parity']['open_ok']} "
-        f"({time.perf_counter() - t_start:.1f} s)")
+    prim = kzg_case(ctx, D, args, curve, log_degree, args.steps, args.warmup, with_h2d=not args.no_h2d, full=full)
+    log(f"primary 2^{log_degree}: {prim['ms_per_step']:.2f} ms/step"
+        + (f", parity {prim['parity']['commit_ok']}/{prim['parity']['open_ok']}" if full else "")
+        + f" ({time.perf_counter() - t_start:.1f} s)")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, prim["last_outputs"])
     sec = None
-    if world == 1 and sec_log and sec_log != log_degree:
+    if full and world == 1 and sec_log and sec_log != log_degree:
         sec = kzg_case(ctx, D, args, curve, sec_log, None, args.warmup, with_h2d=not args.no_h2d)
         log(f"secondary 2^{sec_log}: {sec['ms_per_step']:.2f} ms/step ({time.perf_counter() - t_start:.1f} s)")
 
     # ---- the other BASELINE configs, timed in the same run (N = 1) ------------------------------------------
-    want = args.workloads
+    want = args.workloads if full else "none"
     if want is None:
         want = "latency,batch,ipa,ligero" if world == 1 else "none"
     want = [] if want == "none" else [w.strip() for w in want.split(",") if w.strip()]
@@ -1790,7 +1837,7 @@ def main():
             log(f"workload {name}: {time.perf_counter() - t0:.1f} s")
 
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and rank == 0:      # reported baseline: rank 0 at N = 1 only
+    if full and not args.no_cpu_baseline and world == 1 and rank == 0:      # reported baseline: rank 0 at N = 1 only
         t0 = time.perf_counter()
         import oracle_lib as O
         g = O.gen_bases(curve, 1)[0]
@@ -1802,7 +1849,8 @@ def main():
         srs.free()
         log(f"cpu baseline: {time.perf_counter() - t0:.1f} s")
 
-    all_ok = prim["parity"]["commit_ok"] and prim["parity"]["open_ok"] and (sec is None or (sec["parity"]["commit_ok"] and sec["parity"]["open_ok"]))
+    all_ok = not full or (prim["parity"]["commit_ok"] and prim["parity"]["open_ok"]
+                          and (sec is None or (sec["parity"]["commit_ok"] and sec["parity"]["open_ok"])))
     if rank == 0:
         def cfg(lg):
             return (f"MarlinKZG10<{curve}> commit+open, dense poly deg 2^{lg} per GPU, true SRS resident, hiding off "
@@ -1814,8 +1862,9 @@ def main():
             "ms_per_step": prim["ms_per_step"], "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u32 limbs (381-bit Fq / 255-bit Fr modular integer)", "data": "synthetic",
             "dist": D.info(), "per_rank_ms_per_step": prim["per_rank_ms_per_step"],
-            "parity": dict(prim["parity"], reference_pinned="no -- oracle-only: the reference holds no golden vector on this path and its "
-                                                            "arithmetic crates are not buildable here (DESIGN.md section 2)"),
+            "parity": None if prim["parity"] is None else dict(
+                prim["parity"], reference_pinned="no -- oracle-only: the reference holds no golden vector on this path and its "
+                                                 "arithmetic crates are not buildable here (DESIGN.md section 2)"),
             "config": {"workload": cfg(log_degree), "curve": curve, "log_degree": log_degree,
                        "pairs_per_step": prim["pairs_per_step"], "inflight": max(0, args.inflight),
                        "srs_window_table": bool(args.precompute), "srs_window_table_form": {-1: "library policy (full unless HBM is tight)", 0: "full", 1: "GLV (half size)"}[args.glv_table],

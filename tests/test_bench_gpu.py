@@ -54,8 +54,8 @@ def run_bench(argv, env_extra=None, timeout=900):
 
 
 def test_default_line_small():
-    """Every block of the default (N = 1) line, at scaled-down sizes."""
-    d = run_bench(["--small", "--steps", "3"])
+    """Every block of the --full (N = 1) line, at scaled-down sizes."""
+    d = run_bench(["--full", "--small", "--steps", "3"])
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["unit"] == "pairs/s" and d["value"] > 0
     assert d["parity"]["commit_ok"] and d["parity"]["open_ok"] and d["parity"]["device_poly_eval_ok"]
     assert d["parity"]["commitments_checked"] == 3 and d["parity"]["proofs_checked"] == 3
@@ -85,10 +85,31 @@ def test_default_line_small():
     assert c["workloads"]["latency"]["parity_ok"] is True and c["secondary"]["parity_ok"] is True
 
 
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full: the timed steps and the line only (no parity, roofline, legs or extra blocks), and --dump-outputs writes the
+    last step's commitment and proof -- the same arrays as a --full run of the same arguments, whose in-line parity checks every
+    commitment and proof of its timed region against the closed forms."""
+    small = ["--small", "--steps", "2", "--warmup", "1"]
+    d = run_bench(small + ["--dump-outputs", str(tmp_path / "plain")])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "pairs/s" and d["value"] > 0
+    assert d["value"] == pytest.approx(d["config"]["pairs_per_step"] / (d["ms_per_step"] * 1e-3), rel=1e-6)
+    assert d["parity"] is None and d["roofline"] is None and d["trait_shaped"] is None and d["blocking_msm_ms"] is None
+    for k in ("secondary", "workloads", "cpu_baseline"):
+        assert k not in d, k
+    f = run_bench(small + ["--full", "--no-cpu-baseline", "--workloads", "none", "--no-h2d", "--no-trait", "--secondary-log-degree", "0",
+                           "--dump-outputs", str(tmp_path / "full")])
+    assert f["parity"]["commit_ok"] and f["parity"]["open_ok"] and f["parity"]["commitments_checked"] == 2
+    import numpy as np
+    for name in ("commitment", "proof"):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.size == 24 and (a == np.floor(a)).all() and (a >= 0).all() and (a < 2 ** 32).all()
+        assert (a == b).all(), name
+
+
 def test_two_ranks_self_launched_kzg():
     """`python bench.py --gpus 2 --log-degree 16`: ranks started by the script, each with its REAL chunk of the one true
     SRS, every commitment / proof of the timed region checked against the closed form of the whole polynomial."""
-    d = run_bench(["--gpus", "2", "--log-degree", "16", "--steps", "4", "--no-cpu-baseline"], {"PC_BENCH_DEVICES": "0,0"})
+    d = run_bench(["--full", "--gpus", "2", "--log-degree", "16", "--steps", "4", "--no-cpu-baseline"], {"PC_BENCH_DEVICES": "0,0"})
     assert d["n_gpus"] == 2 and d["dist"]["world_size"] == 2 and len(d["per_rank_ms_per_step"]) == 2
     assert d["config"]["pairs_per_step"] == 2 * 2 * (1 << 16) - 1
     assert d["parity"]["commit_ok"] and d["parity"]["open_ok"]
@@ -97,7 +118,7 @@ def test_two_ranks_self_launched_kzg():
 
 
 def test_two_ranks_blocking_kzg():
-    d = run_bench(["--gpus", "2", "--log-degree", "14", "--steps", "3", "--inflight", "0", "--no-cpu-baseline"], {"PC_BENCH_DEVICES": "0,0"})
+    d = run_bench(["--full", "--gpus", "2", "--log-degree", "14", "--steps", "3", "--inflight", "0", "--no-cpu-baseline"], {"PC_BENCH_DEVICES": "0,0"})
     assert d["n_gpus"] == 2 and d["parity"]["commit_ok"] and d["parity"]["open_ok"]
 
 
@@ -128,7 +149,7 @@ def test_two_ranks_started_by_torchrun_as_the_driver_does(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29791", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log-degree", "14", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -151,7 +172,8 @@ def test_eight_ranks_started_by_torchrun_as_the_driver_does(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "PC_BENCH_FULL_LINE"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", "29793", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--log-degree", "13", "--steps", "3", "--warmup", "1"]
+           "--master-port", "29793", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--log-degree", "13", "--steps", "3", "--warmup", "1",
+           "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

@@ -39,15 +39,21 @@ def _mutated(tmp_path, rel, old, new, count=1):
 
 
 MUTATIONS = [
-    # (file, old, new, what the lint must say)
-    ("src/kzg10_hip.rs", "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), lens.as_ptr(), k,",
-     "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), k,", "arguments"),                       # a dropped argument
-    ("src/kzg10_hip.rs", "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), lens.as_ptr(), k,",
-     "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), ptrs.len(), lens.as_ptr(),", "is an integer"),   # pointer / length swapped
-    ("src/kzg10_hip.rs", "ffi::pc_hip_msm_batch(", "ffi::pc_hip_msm_batched(", "not declared"),                     # a symbol the library does not have
-    ("src/marlin_kzg10.rs", "impl<E, P> PolynomialCommitment<E::ScalarField, P> for HipMarlinKZG10<E, P>",
-     "impl<E, P> PolynomialCommitment<E::ScalarField, P> for HipMarlinKZG10<E, P", "balance"),                      # an unclosed generic list
-    ("src/ipa_pc.rs", "fn check<'a>(vk: &Self::VerifierKey", "fn check(vk: &Self::VerifierKey", "lifetime"),        # a lifetime nobody declares
+    # (file, old, new, what the lint must say); cases whose text holds Rust `::` paths get a short id of their own (`::` separates
+    # the parts of a test id)
+    pytest.param("src/kzg10_hip.rs", "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), lens.as_ptr(), k,",
+                 "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), k,", "arguments",
+                 id="src/kzg10_hip.rs-dropped argument-arguments"),                                                # a dropped argument
+    pytest.param("src/kzg10_hip.rs", "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), lens.as_ptr(), k,",
+                 "ffi::pc_hip_msm_batch(c.raw, key.srs, offs.as_ptr(), ptrs.as_ptr(), ptrs.len(), lens.as_ptr(),", "is an integer",
+                 id="src/kzg10_hip.rs-pointer and length swapped-is an integer"),                                  # pointer / length swapped
+    pytest.param("src/kzg10_hip.rs", "ffi::pc_hip_msm_batch(", "ffi::pc_hip_msm_batched(", "not declared",
+                 id="src/kzg10_hip.rs-undeclared ffi symbol-not declared"),                           # a symbol the library does not have
+    pytest.param("src/marlin_kzg10.rs", "impl<E, P> PolynomialCommitment<E::ScalarField, P> for HipMarlinKZG10<E, P>",
+                 "impl<E, P> PolynomialCommitment<E::ScalarField, P> for HipMarlinKZG10<E, P", "balance",
+                 id="src/marlin_kzg10.rs-unclosed generic list-balance"),                                          # an unclosed generic list
+    pytest.param("src/ipa_pc.rs", "fn check<'a>(vk: &Self::VerifierKey", "fn check(vk: &Self::VerifierKey", "lifetime",
+                 id="src/ipa_pc.rs-undeclared lifetime-lifetime"),                                                 # a lifetime nobody declares
     ("src/kzg10_hip.rs", "pub fn msm_batch_host<G>", "pub fn msm_batch<G>", "defined twice"),                       # two fns of one name
     ("src/lib.rs", "pub mod device;", "pub mod devices;", "no file"),                                               # a module without a file
 ]

@@ -1,14 +1,16 @@
 """The drop-in types override what the reference types override (round-4 review: `HipMarlinKZG10` / `HipIpaPC` inherited the trait's DEFAULT
 `open_combinations`, whose proofs the reference types' `check_combinations` rejects).  No Rust toolchain exists here, so this is a textual
 check: the set of methods inside `impl PolynomialCommitment ... for <ReferenceType>` (poly-commit/src/{marlin/marlin_pc,sonic_pc,ipa_pc}/mod.rs)
-must be a subset of the methods inside the shim's `impl PolynomialCommitment ... for Hip<Type>`.  Skipped where the reference checkout is absent."""
+must be a subset of the methods inside the shim's `impl PolynomialCommitment ... for Hip<Type>`.  The reference types' method names are
+stored in tests/golden/ref_trait_overrides.json (the same parser over the reference's files), so the check needs no reference checkout."""
+import json
 import os
 import re
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/poly-commit/src"
+REF_NAMES = os.path.join(ROOT, "tests", "golden", "ref_trait_overrides.json")
 PAIRS = [("marlin/marlin_pc/mod.rs", "MarlinKZG10", "marlin_kzg10.rs", "HipMarlinKZG10"),
          ("sonic_pc/mod.rs", "SonicKZG10", "sonic_kzg10.rs", "HipSonicKZG10"),
          ("ipa_pc/mod.rs", "InnerProductArgPC", "ipa_pc.rs", "HipIpaPC")]
@@ -34,12 +36,11 @@ def trait_impl_methods(text, type_name):
     return names
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 @pytest.mark.parametrize("ref_file,ref_type,shim_file,shim_type", PAIRS)
 def test_shim_overrides_every_method_the_reference_type_overrides(ref_file, ref_type, shim_file, shim_type):
-    ref = set(trait_impl_methods(open(os.path.join(REF, ref_file)).read(), ref_type))
+    ref = set(json.load(open(REF_NAMES))[ref_type])          # trait_impl_methods over poly-commit/src/<ref_file>
     shim = set(trait_impl_methods(open(os.path.join(ROOT, "rust", "poly-commit-hip", "src", shim_file)).read(), shim_type))
-    assert {"setup", "trim", "commit", "open", "check"} <= ref, ref          # the parser found the impl block
+    assert {"setup", "trim", "commit", "open", "check"} <= ref, ref          # the stored names are the impl block's
     missing = ref - shim
     assert not missing, f"{shim_type} inherits the trait's default for {sorted(missing)}; {ref_type} overrides them"
 

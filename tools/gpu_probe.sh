@@ -8,7 +8,7 @@
 #   VARIANTS  library builds to compare: "default" = poly_commit_amd/libpc_hip.so, any other name = libpc_hip_<name>.so (built here on
 #             the CPU beforehand: PC_HIP_VARIANT=<name> PC_HIP_CXXFLAGS="-D..." python -m poly_commit_amd.build)
 #   RUNS      timed runs per variant, any of:
-#               kzg24 kzg20   bench.py KZG commit+open line (pipelined; blocking MSM and phases in the line)   [KZG_FLAGS extra flags]
+#               kzg24 kzg20   bench.py --full KZG commit+open line (pipelined; blocking MSM and phases in the line)   [KZG_FLAGS extra flags]
 #               ntt           bench.py --workload ntt (config 5)
 #               batch         bench.py --workload batch (config 3)
 #               ipa           tools/ipa_timing.py 22 (config 4)
@@ -30,8 +30,8 @@ for kv in $ENVS; do export "$kv"; done
 VARIANTS=${VARIANTS:-default}
 cmd_of() {
   case $1 in
-    kzg24) echo "python $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --workloads none --no-h2d --no-trait --secondary-log-degree 0 $KZG_FLAGS" ;;
-    kzg20) echo "python $R/bench.py --log-degree 20 --steps 20 --warmup 3 --no-cpu-baseline --workloads none --no-h2d --no-trait --secondary-log-degree 0 $KZG_FLAGS" ;;
+    kzg24) echo "python $R/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --workloads none --no-h2d --no-trait --secondary-log-degree 0 $KZG_FLAGS" ;;
+    kzg20) echo "python $R/bench.py --full --log-degree 20 --steps 20 --warmup 3 --no-cpu-baseline --workloads none --no-h2d --no-trait --secondary-log-degree 0 $KZG_FLAGS" ;;
     ntt)   echo "python $R/bench.py --workload ntt --steps ${NTT_STEPS:-20} --warmup 2 --no-cpu-baseline" ;;
     batch) echo "python $R/bench.py --workload batch --steps ${BATCH_STEPS:-5} --warmup 1 --no-cpu-baseline" ;;
     ipa)   echo "python $R/tools/ipa_timing.py 22" ;;
