@@ -1,11 +1,14 @@
 // Internal interfaces between the translation units of libpc_hip.so.
 //
 // The library is built from several .hip files compiled in parallel (poly_commit_amd/build.py):
-//   abi.hip            the extern "C" entry points (include/pc_hip.h): lifetime, staging, error translation
+//   abi_<subject>.hip  the extern "C" entry points (include/pc_hip.h), one unit per subject: ctx (context, errors, memory, timing),
+//                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa; staging, error translation
+//   key.hpp            host only: the key object (pc_srs), its pipelines and the derived keys of an opening -- their whole lifetime
+//   abi.hpp            host only: the staging helpers more than one abi unit uses
 //   curve_<name>.hip   everything templated on one curve: MSM pipeline, window table, key fold, fixed-base mul
 //   field_<name>.hip   everything templated on one scalar field: NTT, division scan, IPA vector kernels,
 //                      column digests
-// abi.hip reaches the templates through the two tables of plain function pointers below, one
+// The abi units reach the templates through the two tables of plain function pointers below, one
 // instance per curve / field.
 #pragma once
 #include <stddef.h>
