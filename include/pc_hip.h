@@ -290,6 +290,52 @@ int pc_hip_ligero_commit(pc_ctx* ctx, pc_curve field_of, const void* mat, pc_mem
  * column digests, Merkle tree]; a call that ran in slabs reports [0, 0, 0, Merkle tree] (its kernels run under the copies). */
 int pc_hip_last_ligero_phases_ms(const pc_ctx* ctx, float out[4]);
 
+/* ---- The Brakedown linear code (poly-commit/src/linear_codes/brakedown.rs, multilinear_brakedown/mod.rs) ----
+ * A pc_lincode owns the device copy of one code's sparse matrices (BrakedownPCParams::a_mats / b_mats, brakedown.rs:52-55).  The
+ * matrices are sampled from the CALLER's RNG in setup (make_mat, brakedown.rs:305-333): they are an input, the library does not
+ * reproduce arkworks' generator.  A code belongs to its context: it is counted by pc_hip_ctx_bytes_resident (out[0]) and released
+ * with the context if the caller forgot (its handle must still be passed to pc_hip_brakedown_code_free, which then only deletes the
+ * host object).  As for keys (pc_hip_srs_free): pc_hip_brakedown_code_free must not run concurrently with pc_hip_shutdown of the
+ * code's context on another thread -- before or after it, never beside it. */
+typedef struct pc_lincode pc_lincode;
+
+/* Replaces holding BrakedownPCParams::{a_dims, b_dims, a_mats, b_mats, start, end, m_ext} on the host (brakedown.rs:146-203).
+ * Flat host arrays, the n_levels A matrices first, then the n_levels B matrices:
+ *   dims     3 numbers (n rows, m columns, d non-zeros per row) per matrix
+ *   ind_ptr  m + 1 numbers per matrix, SprsMat::ind_ptr (linear_codes/utils.rs:31-36), each matrix counting from 0
+ *   col_ind  nnz row indices, the matrices' entries back to back; val: nnz field elements (Montgomery), likewise
+ * Checked on the host before the device is touched: ind_ptr monotone and consistent with nnz, every col_ind below n of its matrix,
+ * the chain a_dims[i+1].n == a_dims[i].m with a_dims[0].n == msg_len, b_dims[i].n == end[i] - start[i], codeword_len ==
+ * codeword_len(a_dims, b_dims) (brakedown.rs:292-299); with n_levels == 0 the code is the base code alone and any codeword_len >=
+ * msg_len is taken (brakedown.rs:163-164).  Anything else is PC_ERR_INVALID_ARG and *out stays NULL.  The arrays are copied: the
+ * caller may free them when the call returns. */
+int pc_hip_brakedown_code_create(pc_ctx* ctx, pc_curve field_of, size_t msg_len, size_t codeword_len, size_t n_levels,
+                                 const size_t* dims, const size_t* ind_ptr, const uint32_t* col_ind, const void* val, size_t nnz,
+                                 pc_lincode** out);
+void pc_hip_brakedown_code_free(pc_lincode* code);
+/* BrakedownPCParams::m_ext (brakedown.rs:163-167); 0 for NULL */
+size_t pc_hip_brakedown_codeword_len(const pc_lincode* code);
+
+/* MultilinearBrakedown::encode (multilinear_brakedown/mod.rs:56-84) for `rows` messages at once (LinearEncode::compute_matrices
+ * encodes every row, linear_codes/mod.rs:131-135; check encodes v and the well-formedness vector, :470-480): msgs is rows x msg_len,
+ * out rows x codeword_len, row-major, Montgomery in, canonical Montgomery residues out, host or device on either side.  The A
+ * chain, naive_reed_solomon (:111-122, Horner at the points 1, 2, 3, ..) and the B products of the loop at :79-82 exactly as
+ * written there -- level 0 first, so a level reads zeros where the later levels write. */
+int pc_hip_brakedown_encode(pc_ctx* ctx, const pc_lincode* code, const void* msgs, pc_mem where_in, size_t rows, void* out,
+                            pc_mem where_out);
+
+/* LinearCodePCS::commit steps 1-3 (linear_codes/mod.rs:248-277) with the Brakedown code, like pc_hip_ligero_commit: encode the
+ * rows x msg_len matrix, digest the codeword_len columns (pc_hip_column_hash), build the Merkle tree over them (pc_hip_merkle_tree:
+ * the leaves are padded to 2^h, codeword_len is no power of two).  nodes_out_host: (2^h - 1) x 32 bytes; leaves_out_host
+ * (codeword_len x 32 bytes) and ext_out (rows x codeword_len, host or device per where_ext) may be NULL.  Same bits as the three
+ * steps called one by one. */
+int pc_hip_brakedown_commit(pc_ctx* ctx, const pc_lincode* code, const void* mat, pc_mem where_in, size_t rows, pc_hash col_hash,
+                            pc_hash tree_hash, int len_prefix, void* ext_out, pc_mem where_ext, void* leaves_out_host,
+                            void* nodes_out_host);
+/* Kernel-only milliseconds of the last pc_hip_brakedown_commit (timing on): [transpose in + A chain + base code, B products,
+ * column digests, Merkle tree]; after pc_hip_brakedown_encode the first two. */
+int pc_hip_last_brakedown_phases_ms(const pc_ctx* ctx, float out[4]);
+
 /* out[i] = sum_j xi[j] * polys[j][i] for i < n_out (coefficients past lens[j] are zero): the
  * random linear combination MarlinKZG10::open forms before the one witness division,
  * poly-commit/src/marlin/marlin_pc/mod.rs:281-287 (and :291-301 for the shifted polynomials).

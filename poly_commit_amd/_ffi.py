@@ -93,6 +93,14 @@ def load_library():
     lib.pc_hip_merkle_tree.argtypes = [vp, ip, vp, ip, sz, ip, vp, ip]
     lib.pc_hip_ligero_commit.argtypes = [vp, ip, vp, ip, sz, sz, C.c_uint, ip, ip, ip, vp, ip, vp, vp]
     lib.pc_hip_last_ligero_phases_ms.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.pc_hip_brakedown_code_create.argtypes = [vp, ip, sz, sz, sz, vp, vp, vp, vp, sz, C.POINTER(vp)]
+    lib.pc_hip_brakedown_code_free.argtypes = [vp]
+    lib.pc_hip_brakedown_code_free.restype = None
+    lib.pc_hip_brakedown_codeword_len.argtypes = [vp]
+    lib.pc_hip_brakedown_codeword_len.restype = sz
+    lib.pc_hip_brakedown_encode.argtypes = [vp, vp, vp, ip, sz, vp, ip]
+    lib.pc_hip_brakedown_commit.argtypes = [vp, vp, vp, ip, sz, ip, ip, ip, vp, ip, vp, vp]
+    lib.pc_hip_last_brakedown_phases_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.pc_hip_fr_lincomb.argtypes = [vp, ip, C.POINTER(vp), ip, C.POINTER(sz), sz, vp, vp, ip, sz]
     lib.pc_hip_fr_fold.argtypes = [vp, ip, vp, vp, sz, vp]
     lib.pc_hip_fr_dot.argtypes = [vp, ip, vp, vp, sz, vp]
@@ -399,6 +407,15 @@ class Context:
     def upload_srs(self, curve, bases, n=None, stride_bytes=0):
         return Srs(self, curve, bases, n, stride_bytes)
 
+    def brakedown_code(self, curve, msg_len, codeword_len, dims=(), ind_ptr=(), col_ind=(), val=None):
+        """Resident Brakedown code (pc_hip_brakedown_code_create) from the caller's sampled matrices."""
+        return BrakedownCode(self, curve, msg_len, codeword_len, dims, ind_ptr, col_ind, val)
+
+    def last_brakedown_phases_ms(self):
+        out = (C.c_float * 4)()
+        self.check(self.lib.pc_hip_last_brakedown_phases_ms(self.h, out))
+        return list(out)
+
     def bytes_resident(self):
         """pc_hip_ctx_bytes_resident: device bytes by kind."""
         out = (C.c_size_t * 6)()
@@ -418,6 +435,57 @@ class Context:
         srs = Srs.__new__(Srs)
         srs.ctx, srs.curve, srs.h, srs.n = self, curve, h, npts.value
         return srs, used.value
+
+
+class BrakedownCode:
+    """Resident sparse matrices of one Brakedown code (pc_lincode).  dims: (n, m, d) per matrix, the A matrices first, then the B
+    matrices; ind_ptr: m + 1 numbers per matrix, each matrix counting from 0; col_ind / val ((nnz, 4) uint64, Montgomery): the
+    matrices' entries back to back.  The library copies the arrays: nothing of them is referenced after construction."""
+
+    def __init__(self, ctx, curve, msg_len, codeword_len, dims=(), ind_ptr=(), col_ind=(), val=None):
+        self.ctx, self.curve, self.msg_len = ctx, curve, msg_len
+        dims = np.ascontiguousarray(dims, dtype=np.uintp).reshape(-1)
+        ind_ptr = np.ascontiguousarray(ind_ptr, dtype=np.uintp).reshape(-1)
+        col_ind = np.ascontiguousarray(col_ind, dtype=np.uint32).reshape(-1)
+        val = np.zeros((0, 4), dtype=np.uint64) if val is None else np.ascontiguousarray(val, dtype=np.uint64).reshape(-1, 4)
+        assert len(dims) % 6 == 0 and len(val) == len(col_ind)
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pc_hip_brakedown_code_create(ctx.h, CURVES[curve], msg_len, codeword_len, len(dims) // 6, dims.ctypes.data, ind_ptr.ctypes.data,
+                                                       col_ind.ctypes.data, val.ctypes.data, len(col_ind), C.byref(h)))
+        self.h = h
+        self.codeword_len = int(ctx.lib.pc_hip_brakedown_codeword_len(h))
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.pc_hip_brakedown_code_free(self.h)
+            self.h = None
+
+    def encode(self, msgs, rows=None, out=None):
+        """rows x msg_len (Montgomery) -> rows x codeword_len, row-major: numpy in -> numpy out; torch cuda tensors / device pointers
+        (with rows, out) stay on the device."""
+        pin, win = _ptr(msgs)
+        if rows is None:
+            rows = msgs.shape[0]
+        if out is None:
+            assert win == PC_MEM_HOST
+            out = np.zeros((rows, self.codeword_len, 4), dtype=np.uint64)
+        pout, wout = _ptr(out)
+        self.ctx.check(self.ctx.lib.pc_hip_brakedown_encode(self.ctx.h, self.h, pin, win, rows, pout, wout))
+        return out
+
+    def commit(self, mat, rows=None, col_hash="blake2s", tree_hash="sha256", len_prefix=True, ext_out=None, want_leaves=True):
+        """LinearCodePCS::commit steps 1-3 (pc_hip_brakedown_commit): (nodes (2^h - 1, 32) uint8, root first; leaves (codeword_len, 32) or None)."""
+        pin, win = _ptr(mat)
+        if rows is None:
+            rows = mat.shape[0]
+        hid = {"sha256": 0, "blake2s": 1}
+        n = self.codeword_len
+        nodes = np.zeros(((1 << max(1, (n - 1).bit_length())) - 1, 32), dtype=np.uint8)
+        leaves = np.zeros((n, 32), dtype=np.uint8) if want_leaves else None
+        pext, wext = _ptr(ext_out) if ext_out is not None else (None, PC_MEM_HOST)
+        self.ctx.check(self.ctx.lib.pc_hip_brakedown_commit(self.ctx.h, self.h, pin, win, rows, hid[col_hash], hid[tree_hash], 1 if len_prefix else 0,
+                                                            pext, wext, leaves.ctypes.data if want_leaves else None, nodes.ctypes.data))
+        return nodes, leaves
 
 
 class Srs:

@@ -28,3 +28,7 @@ struct Staged {
   }
   ~Staged() { if (owned) be.free(dev); }
 };
+
+// pc_hip_shutdown's share of the Brakedown code objects (abi_lincode.hip): their device memory goes, a code its caller still holds
+// stays behind as a tombstone that pc_hip_brakedown_code_free only deletes
+void lincodes_shutdown(pc_ctx* ctx);

@@ -27,7 +27,7 @@ int pc_hip_init(int device_id, pc_ctx** out) {
 void pc_hip_shutdown(pc_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  { std::lock_guard<std::recursive_mutex> lk(ctx->mu); keys_shutdown(ctx); }
+  { std::lock_guard<std::recursive_mutex> lk(ctx->mu); keys_shutdown(ctx); lincodes_shutdown(ctx); }
   ctx->ntt_plans.clear();
   if (ctx->epoch) (void)hipEventDestroy(ctx->epoch);
   for (hipStream_t q : ctx->lig_out_q) if (q) (void)hipStreamDestroy(q);

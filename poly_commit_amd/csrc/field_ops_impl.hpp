@@ -7,6 +7,7 @@
 #include "poly.hpp"
 #include "ipa.hpp"
 #include "hash.hpp"
+#include "sprs.hpp"
 
 namespace pc {
 
@@ -97,9 +98,12 @@ struct FieldOpsImpl {
     if (hash == PC_HASH_SHA256) { ColumnHashPartBody<FrP, Sha256> b{e, rows, n_cols, rows_total, col0, (uint32_t)first, (uint32_t)last, state, o}; be.launch(b, cols, 64); }
     else { ColumnHashPartBody<FrP, Blake2s256> b{e, rows, n_cols, rows_total, col0, (uint32_t)first, (uint32_t)last, state, o}; be.launch(b, cols, 64); }
   }
+  static void brakedown_encode_f(HipBackend& be, const BrakedownDev& code, const uint32_t* msgs, uint32_t rows, uint32_t* T, uint32_t* out) {
+    brakedown_encode<FrP>(be, code, msgs, rows, T, out);
+  }
   static FieldOps table() {
     return FieldOps{&make_ntt, &poly_eval_f, &div_scan_f, &witness_f, &fr_fold, &fr_dot, &ipa_fold_dots, &fr_powers, &ipa_key_scalars, &fr_lincomb, &column_hash,
-                    &column_hash_part};
+                    &column_hash_part, &brakedown_encode_f, &brakedown_points<FrP>};
   }
 };
 

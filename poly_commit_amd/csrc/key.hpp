@@ -41,6 +41,8 @@ struct pc_ctx {
   std::vector<struct pc_srs*> keys;   // every key object of this context that is alive (pc_hip_ctx_bytes_resident, pc_hip_ctx_trim)
   // pc_hip_ipa_open_rounds: the powers of z, the per-base factors of the fixed key and the two scalar vectors of its rounds (grow-only, pc_hip_ctx_trim frees them)
   void* ipa_buf[3] = {nullptr, nullptr, nullptr}; size_t ipa_bytes[3] = {0, 0, 0};
+  std::vector<struct pc_lincode*> codes;   // every Brakedown code object of this context that is alive; abi_lincode.hip alone creates and releases them
+  float brakedown_phases[4] = {0, 0, 0, 0};
 };
 
 // Independent pipelines per SRS (stream + workspace each), used round-robin; a pipeline that still

@@ -2,12 +2,13 @@
 //
 // The library is built from several .hip files compiled in parallel (poly_commit_amd/build.py):
 //   abi_<subject>.hip  the extern "C" entry points (include/pc_hip.h), one unit per subject: ctx (context, errors, memory, timing),
-//                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa; staging, error translation
+//                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa, lincode (the Brakedown code object); staging,
+//                      error translation
 //   key.hpp            host only: the key object (pc_srs), its pipelines and the derived keys of an opening -- their whole lifetime
 //   abi.hpp            host only: the staging helpers more than one abi unit uses
 //   curve_<name>.hip   everything templated on one curve: MSM pipeline, window table, key fold, fixed-base mul
 //   field_<name>.hip   everything templated on one scalar field: NTT, division scan, IPA vector kernels,
-//                      column digests
+//                      column digests, the Brakedown encoder (sprs.hpp)
 // The abi units reach the templates through the two tables of plain function pointers below, one
 // instance per curve / field.
 #pragma once
@@ -16,6 +17,7 @@
 #include "../../include/pc_hip.h"
 #include "hip_backend.hpp"
 #include "msm.hpp"
+#include "sprs.hpp"
 
 namespace pc {
 
@@ -83,6 +85,9 @@ struct FieldOps {
   // one slab of rows absorbed into the per-column chaining states (hash.hpp, ColumnHashPartBody); columns [col0, col0 + cols)
   void (*column_hash_part)(HipBackend& be, int hash, const uint32_t* ext, uint32_t rows, uint32_t n_cols, uint32_t rows_total, uint32_t col0,
                            uint32_t cols, int first, int last, uint32_t* state, uint32_t* out);
+  // one Brakedown encode of `rows` messages (sprs.hpp): row-major in and out, T = the transposed working buffer; two phase marks
+  void (*brakedown_encode)(HipBackend& be, const BrakedownDev& code, const uint32_t* msgs, uint32_t rows, uint32_t* T, uint32_t* out);
+  void (*brakedown_points)(uint32_t* out_host, size_t count);      // the base code's points 1, 2, .. in Montgomery form (host)
 };
 
 // (accessor functions rather than global tables: a namespace-scope constant would also be emitted into the

@@ -125,15 +125,18 @@ struct LinearCodePCS {
   }
   // Merkle authentication path of column `index` out of the commitment state (col_tree.generate_proof,
   // mod.rs:555-557): the sibling leaf digest, then the sibling inner nodes from the bottom up.
-  static void merkle_path(const LinCodePCCommitmentState<E>& st, size_t index, uint8_t leaf_sibling[32],
+  // (returns false when the sibling is one of the empty leaves the tree was padded with: a codeword length that is no power of two)
+  static bool merkle_path(const LinCodePCCommitmentState<E>& st, size_t index, uint8_t leaf_sibling[32],
                           std::vector<uint8_t>& path) {
     const size_t n_inner = st.nodes.size() / 32;
-    memcpy(leaf_sibling, st.leaves.data() + (index ^ 1) * 32, 32);
+    const bool present = ((index ^ 1) + 1) * 32 <= st.leaves.size();
+    if (present) memcpy(leaf_sibling, st.leaves.data() + (index ^ 1) * 32, 32); else memset(leaf_sibling, 0, 32);
     path.clear();
     for (size_t node = (n_inner + index + 1) / 2 - 1; node > 0; node = (node - 1) / 2) {
       const size_t sib = (node & 1) ? node + 1 : node - 1;
       path.insert(path.end(), st.nodes.begin() + sib * 32, st.nodes.begin() + (sib + 1) * 32);
     }
+    return present;
   }
 
   // ---- open / check (linear_codes/mod.rs:300-503, generate_proof :523-565).  The sponge is the caller's: the t query
@@ -141,6 +144,7 @@ struct LinearCodePCS {
   struct ProofSingle {                               // LinCodePCProof { opening: LinCodePCProofSingle { paths, v, columns }, well_formedness }
     std::vector<size_t> leaf_index;
     std::vector<std::array<uint8_t, 32>> leaf_sibling;
+    std::vector<uint8_t> leaf_sibling_absent;        // per query, 1: the sibling is an empty padding leaf (empty vector: none is)
     std::vector<std::vector<uint8_t>> paths;         // per query: sibling inner nodes, bottom-up
     std::vector<FrT<E>> v;
     std::vector<std::vector<FrT<E>>> columns;
@@ -160,10 +164,11 @@ struct LinearCodePCS {
     if (tree_hash == PC_HASH_SHA256) Sha256Host::digest(data, len, out); else Blake2s::digest(data, len, out);
   }
   // Path::verify for the byte-digest Config: bottom level D(conv(l) || conv(r)), upper levels D(left || right)
-  bool verify_path(const uint8_t root[32], const uint8_t leaf[32], size_t index, const uint8_t sibling[32], const std::vector<uint8_t>& path) const {
+  bool verify_path(const uint8_t root[32], const uint8_t leaf[32], size_t index, const uint8_t sibling[32], const std::vector<uint8_t>& path,
+                   bool sibling_absent = false) const {
     uint8_t buf[96], cur[32]; size_t n = 0;
-    auto put = [&](const uint8_t* d) { if (len_prefix) { uint64_t l = 32; memcpy(buf + n, &l, 8); n += 8; } memcpy(buf + n, d, 32); n += 32; };
-    if (index % 2 == 0) { put(leaf); put(sibling); } else { put(sibling); put(leaf); }
+    auto put = [&](const uint8_t* d, size_t len = 32) { if (len_prefix) { uint64_t l = len; memcpy(buf + n, &l, 8); n += 8; } memcpy(buf + n, d, len); n += len; };
+    if (index % 2 == 0) { put(leaf); put(sibling, sibling_absent ? 0 : 32); } else { put(sibling, sibling_absent ? 0 : 32); put(leaf); }
     two_to_one(buf, n, cur);
     index /= 2;
     for (size_t k = 0; k + 32 <= path.size(); k += 32, index /= 2) {
@@ -174,8 +179,13 @@ struct LinearCodePCS {
   }
   Error open(pc_ctx* ctx, const LinCodePCCommitment& com, const LinCodePCCommitmentState<E>& st, const FrT<E>& z,
              const std::vector<size_t>& indices, const std::vector<FrT<E>>* r, ProofSingle& proof) const {
-    if (st.ext_mat.entries.empty()) { Error e; e.kind = Error::Backend; e.msg = "open needs the encoded matrix in the commitment state"; return e; }
     std::vector<FrT<E>> a, b; tensor(z, com.metadata.n_cols, com.metadata.n_rows, a, b);
+    return open_tensored(ctx, st, b, indices, r, proof);
+  }
+  // the same with the caller's tensor (a scheme whose L::tensor is not the univariate one: the multilinear codes)
+  Error open_tensored(pc_ctx* ctx, const LinCodePCCommitmentState<E>& st, const std::vector<FrT<E>>& b, const std::vector<size_t>& indices,
+                      const std::vector<FrT<E>>* r, ProofSingle& proof) const {
+    if (st.ext_mat.entries.empty()) { Error e; e.kind = Error::Backend; e.msg = "open needs the encoded matrix in the commitment state"; return e; }
     proof = ProofSingle();
     if (r) { if (Error e = row_mul(ctx, st.mat, *r, proof.well_formedness)) return e; proof.has_well_formedness = true; }     // :343-349
     if (Error e = row_mul(ctx, st.mat, b, proof.v)) return e;                                                              // generate_proof 1.
@@ -185,14 +195,22 @@ struct LinearCodePCS {
       for (size_t row = 0; row < st.ext_mat.n; row++) col[row] = st.ext_mat.entries[row * st.ext_mat.m + idx];
       proof.columns.push_back(col);
       std::array<uint8_t, 32> sib; std::vector<uint8_t> path;
-      merkle_path(st, idx, sib.data(), path);
-      proof.leaf_index.push_back(idx); proof.leaf_sibling.push_back(sib); proof.paths.push_back(path);
+      const bool present = merkle_path(st, idx, sib.data(), path);
+      proof.leaf_index.push_back(idx); proof.leaf_sibling.push_back(sib); proof.paths.push_back(path); proof.leaf_sibling_absent.push_back(present ? 0 : 1);
     }
     return Error();
   }
   // ok == false: the claimed value is wrong (:494-499); Error::InvalidCommitment: a path, an index or an inner product fails
   Error check(pc_ctx* ctx, const LinCodePCCommitment& com, const LigeroPCParams& param, const FrT<E>& z, const FrT<E>& value,
               const ProofSingle& proof, const std::vector<size_t>& indices, const std::vector<FrT<E>>* r, bool& ok) const {
+    std::vector<FrT<E>> a, b; tensor(z, com.metadata.n_cols, com.metadata.n_rows, a, b);
+    return check_tensored(ctx, com, a, b, value, proof, indices, r, ok, true,
+                          [&](const std::vector<FrT<E>>& v, std::vector<FrT<E>>& w) { return LinearEncode<E>::reed_solomon(ctx, v, param.rho_inv, w); });
+  }
+  // the same with the caller's tensor and encoder; pow2_ext: the codeword length must be a power of two (the FFT codes)
+  template <class Enc>
+  Error check_tensored(pc_ctx* ctx, const LinCodePCCommitment& com, const std::vector<FrT<E>>& a, const std::vector<FrT<E>>& b, const FrT<E>& value,
+                       const ProofSingle& proof, const std::vector<size_t>& indices, const std::vector<FrT<E>>* r, bool& ok, bool pow2_ext, Enc encode) const {
     ok = false;
     const size_t n_rows = com.metadata.n_rows, n_cols = com.metadata.n_cols, n_ext = com.metadata.n_ext_cols, t = indices.size();
     if ((r != nullptr) != proof.has_well_formedness) return invalid_commitment("well-formedness proof missing or unexpected");
@@ -201,7 +219,7 @@ struct LinearCodePCS {
     unsigned height = 1; while (((size_t)1 << height) < n_ext) height++;
     if (proof.columns.size() != t || proof.paths.size() != t || proof.leaf_index.size() != t || proof.leaf_sibling.size() != t ||
         proof.v.size() != n_cols || (r && proof.well_formedness.size() != n_cols) || (r && r->size() != n_rows) ||
-        n_ext == 0 || (n_ext & (n_ext - 1)) || n_ext < n_cols)
+        n_ext == 0 || (pow2_ext && (n_ext & (n_ext - 1))) || n_ext < n_cols || (!proof.leaf_sibling_absent.empty() && proof.leaf_sibling_absent.size() != t))
       return invalid_commitment("proof shape");
     for (size_t j = 0; j < t; j++)
       if (indices[j] >= n_ext || proof.paths[j].size() != (size_t)32 * (height - 1)) return invalid_commitment("proof shape");
@@ -212,13 +230,13 @@ struct LinearCodePCS {
     int rc = t ? pc_hip_column_hash(ctx, E::ID, m.data(), PC_MEM_HOST, n_rows, t, col_hash, digests.data(), PC_MEM_HOST) : PC_OK;
     if (rc != PC_OK) { Error e; e.kind = Error::Backend; e.msg = pc_hip_strerror(rc); return e; }
     for (size_t j = 0; j < t; j++)                                                                                          // 4.
-      if (proof.leaf_index[j] != indices[j] || !verify_path(com.root, &digests[j * 32], indices[j], proof.leaf_sibling[j].data(), proof.paths[j]))
+      if (proof.leaf_index[j] != indices[j] || !verify_path(com.root, &digests[j * 32], indices[j], proof.leaf_sibling[j].data(), proof.paths[j],
+                                                         !proof.leaf_sibling_absent.empty() && proof.leaf_sibling_absent[j]))
         return invalid_commitment("Merkle path");
     std::vector<FrT<E>> w, wwf;                                                                                             // 5.
-    if (Error e = LinearEncode<E>::reed_solomon(ctx, proof.v, param.rho_inv, w)) return e;
-    if (r) if (Error e = LinearEncode<E>::reed_solomon(ctx, proof.well_formedness, param.rho_inv, wwf)) return e;
+    if (Error e = encode(proof.v, w)) return e;
+    if (r) if (Error e = encode(proof.well_formedness, wwf)) return e;
     if (w.size() != n_ext) return invalid_commitment("encoding length");
-    std::vector<FrT<E>> a, b; tensor(z, n_cols, n_rows, a, b);                                                               // 6.
     auto ip = [](const std::vector<FrT<E>>& x, const std::vector<FrT<E>>& y) { FrT<E> acc = FrT<E>::zero(); for (size_t i = 0; i < x.size() && i < y.size(); i++) acc = acc + x[i] * y[i]; return acc; };
     for (size_t j = 0; j < t; j++) {                                                                                         // 7.
       if (r && !(ip(*r, proof.columns[j]) == wwf[indices[j]])) return invalid_commitment("well-formedness inner product");

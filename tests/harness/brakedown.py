@@ -1,0 +1,457 @@
+"""The Brakedown linear code and MultilinearBrakedown (poly-commit/src/linear_codes/brakedown.rs, multilinear_brakedown/mod.rs):
+
+  1. a pure-Python restatement on canonical integers -- default dimensions (`f64` exactly as the reference), make_mat over a seeded
+     generator in the reference's draw order, SprsMat, encode with the loop of mod.rs:79-82 AS WRITTEN (level 0 first), commit
+     through hashlib, open, check.  It is the checker of the device path (oracle/ holds the checkers of the older schemes).
+  2. the driver of the device path above the C ABI: the code uploaded once (pc_hip_brakedown_code_create), commit
+     (pc_hip_brakedown_commit), open (the row combinations and column gathers of tests/harness/ligero.py), check (received columns
+     hashed on the device, v and the well-formedness vector encoded by pc_hip_brakedown_encode).
+
+The matrices are an input of the library: arkworks' RNG is not reproduced, `Gen` below stands for the caller's.  The sponge is the
+caller's too: query indices and the vector r are arguments.
+"""
+import math
+import os
+import subprocess
+from operator import mul
+
+import numpy as np
+
+import pyref as R
+
+ALPHA, BETA, RHO_INV, BASE_LEN, SEC_PARAM = (178, 1000), (61, 1000), (1521, 1000), 30, 128      # brakedown.rs:111-115
+M64 = (1 << 64) - 1
+FIELD_ID = {"bls12_381": 0, "bn254": 1, "pallas": 2}          # pc_curve
+TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(TESTS)
+_R = 1 << 256
+
+
+class InvalidCommitment(ValueError):
+    """linear_codes Error::InvalidCommitment."""
+
+
+def field_p(curve):
+    return R.FIELDS[R.CURVES[curve]["fr"]]["p"]
+
+
+def monts(curve, vals):
+    p = field_p(curve)
+    return np.frombuffer(b"".join((v % p * _R % p).to_bytes(32, "little") for v in vals), dtype="<u8").astype(np.uint64).reshape(-1, 4)
+
+
+def ints(curve, arr):
+    p = field_p(curve)
+    rinv = pow(_R, -1, p)
+    raw = np.ascontiguousarray(arr, dtype="<u8").reshape(-1, 4).tobytes()
+    return [int.from_bytes(raw[32 * i:32 * i + 32], "little") * rinv % p for i in range(len(raw) // 32)]
+
+
+# ---- dimensions (poly-commit/src/utils.rs:26-45, brakedown.rs:103-143, :204-299) ---------------------------------------------------
+def ent(x):
+    assert 0.0 <= x <= 1.0
+    return 0.0 if x in (0.0, 1.0) else -x * math.log2(x) - (1.0 - x) * math.log2(1.0 - x)
+
+
+def ceil_mul(a, b):
+    return (a * b[0] + b[1] - 1) // b[1]
+
+
+def ceil_div(x, y):
+    return (x + y - 1) // y
+
+
+def _div(a):
+    return a[0] / a[1]
+
+
+def cn_const(a=ALPHA, b=BETA):
+    a, b = _div(a), _div(b)
+    arg = 1.28 * b / a
+    return ent(b) + a * ent(arg), -b * math.log2(arg)
+
+
+def dn_const(a=ALPHA, b=BETA, r=RHO_INV):
+    m = (r[0] * (a[1] - a[0]) - r[1] * a[1]) / (r[1] * a[1])                                    # mu = rho_inv - 1 - rho_inv * alpha
+    c = (3, 100)
+    n = (b[0] * (a[1] + a[0]) * c[1] + c[0] * b[1] * a[1]) / (b[1] * a[1] * c[1])            # nu = beta + alpha * beta + 0.03
+    a, b, r = _div(a), _div(b), _div(r)
+    nm = n / m
+    return r * a * ent(b / r) + m * ent(nm), -a * b * math.log2(nm)
+
+
+def cn(n, c, b=BETA):
+    return min(max(ceil_mul(n, (32 * b[0], 25 * b[1])), 4 + ceil_mul(n, b)), math.ceil((110.0 / float(n) + c[0]) / c[1]))
+
+
+def dn(n, d, bits, b=BETA, r=RHO_INV):
+    return min(ceil_mul(n, (2 * b[0], b[1])) + math.ceil(float(ceil_mul(n, r) - n + 110) / float(bits)), math.ceil((110.0 / float(n) + d[0]) / d[1]))
+
+
+def mat_size(n, bits, base_len=BASE_LEN, a=ALPHA, r=RHO_INV):
+    """brakedown.rs:260-288 -> (a_dims, b_dims), each (n, m, d)."""
+    c, d = cn_const(), dn_const()
+    a_dims = []
+    while n >= base_len:
+        m = ceil_mul(n, a)
+        a_dims.append((n, m, min(cn(n, c), m)))
+        n = m
+    b_dims = []
+    for an, am, _ in a_dims:
+        bn = ceil_mul(am, r)
+        bm = ceil_mul(an, r) - an - bn
+        b_dims.append((bn, bm, min(dn(bn, d, bits), bm)))
+    return a_dims, b_dims
+
+
+def codeword_len(a_dims, b_dims):
+    return sum(x[1] for x in b_dims) + sum(x[0] for x in a_dims) + b_dims[-1][0]
+
+
+def distance():
+    return (RHO_INV[1] * BETA[0], RHO_INV[0] * BETA[1])
+
+
+def default_shape(poly_len, bits):
+    """BrakedownPCParams::default (brakedown.rs:116-122): (n rows, m message length, a_dims, b_dims, m_ext)."""
+    t = R.calculate_t(bits, SEC_PARAM, distance(), poly_len)
+    n = 1 << R.ark_log2(math.ceil(math.sqrt(float(ceil_div(2 * poly_len, t)))))
+    m = ceil_div(poly_len, n)
+    a_dims, b_dims = mat_size(m, bits)
+    return n, m, a_dims, b_dims, (codeword_len(a_dims, b_dims) if a_dims else ceil_mul(m, RHO_INV))
+
+
+# ---- the caller's generator, SprsMat, make_mat ----------------------------------------------------------------------------------------
+class Gen:
+    """A counter-based generator (splitmix64) standing for the caller's RngCore: next_u64, and a non-zero field element made of four
+    draws (low word first) cut to the bits below the modulus' top bit.  tests/cpp/brakedown_driver.cpp holds the same one."""
+
+    def __init__(self, seed):
+        self.s = seed & M64
+
+    def next_u64(self):
+        self.s = (self.s + 0x9E3779B97F4A7C15) & M64
+        z = self.s
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+        return z ^ (z >> 31)
+
+    def nonzero(self, p):
+        mask = (1 << (p.bit_length() - 1)) - 1
+        while True:
+            v = sum(self.next_u64() << (64 * i) for i in range(4)) & mask
+            if v:
+                return v
+
+
+class SprsMat:
+    """linear_codes/utils.rs:20-107: CSC."""
+
+    def __init__(self, n, m, d, ind_ptr, col_ind, val):
+        self.n, self.m, self.d, self.ind_ptr, self.col_ind, self.val = n, m, d, ind_ptr, col_ind, val
+        self._cols = None
+
+    @classmethod
+    def new_from_flat(cls, n, m, d, flat):
+        assert len(flat) == m * n
+        ind_ptr, col_ind, val = [0] * (m + 1), [], []
+        for i in range(m):
+            for c, v in enumerate(flat[i * n:(i + 1) * n]):
+                if v != 0:
+                    ind_ptr[i + 1] += 1
+                    col_ind.append(c)
+                    val.append(v)
+            ind_ptr[i + 1] += ind_ptr[i]
+        assert ind_ptr[m] <= d * n
+        return cls(n, m, d, ind_ptr, col_ind, val)
+
+    @classmethod
+    def new_from_columns(cls, n, m, d, cols):
+        assert len(cols) == m
+        ind_ptr, col_ind, val = [0] * (m + 1), [], []
+        for j in range(m):
+            for i, v in cols[j]:
+                col_ind.append(i)
+                val.append(v)
+            assert len(cols[j]) <= n
+            ind_ptr[j + 1] = ind_ptr[j] + len(cols[j])
+        assert ind_ptr[m] <= d * n
+        return cls(n, m, d, ind_ptr, col_ind, val)
+
+    def row_mul(self, v, p, clip=None):
+        """v.M (utils.rs:41-52).  clip: entries whose row index is >= clip are left out (the concurrent form of the B products)."""
+        if self._cols is None or self._cols[0] != clip:
+            cols = []
+            for j in range(self.m):
+                a, b = self.ind_ptr[j], self.ind_ptr[j + 1]
+                keep = [k for k in range(a, b) if clip is None or self.col_ind[k] < clip]
+                cols.append(([self.col_ind[k] for k in keep], [self.val[k] for k in keep]))
+            self._cols = (clip, cols)
+        return [sum(map(mul, [v[i] for i in ci], x)) % p for ci, x in self._cols[1]]
+
+
+def make_mat(n, m, d, gen, p):
+    """brakedown.rs:305-333 in its draw order: the d column indices of a row first (Fisher-Yates on a list that is NOT reset between
+    rows), then the d values."""
+    tmp = list(range(m))
+    cols = [[] for _ in range(m)]
+    for i in range(n):
+        idxs = []
+        for j in range(d):
+            r = gen.next_u64() % (m - j)
+            tmp[r], tmp[m - 1 - j] = tmp[m - 1 - j], tmp[r]
+            idxs.append(tmp[m - 1 - j])
+        for j in idxs:
+            cols[j].append((i, gen.nonzero(p)))
+    return SprsMat.new_from_columns(n, m, d, cols)
+
+
+class Code:
+    """BrakedownPCParams::new (brakedown.rs:146-203): the fields encode needs."""
+
+    def __init__(self, curve, m, a_dims, b_dims, a_mats, b_mats, m_ext=None):
+        self.curve, self.p, self.m, self.a_dims, self.b_dims, self.a_mats, self.b_mats = curve, field_p(curve), m, a_dims, b_dims, a_mats, b_mats
+        self.m_ext = (m_ext if m_ext is not None else ceil_mul(m, RHO_INV)) if not a_dims else codeword_len(a_dims, b_dims)
+        self.start, self.end, acc = [], [], 0
+        for row, _, _ in a_dims:
+            acc += row
+            self.start.append(acc)
+        acc = self.m_ext
+        for _, col, _ in b_dims:
+            acc -= col
+            self.end.append(acc)
+
+    @property
+    def nnz(self):
+        return sum(len(x.val) for x in self.a_mats + self.b_mats)
+
+    def flat(self):
+        """The arguments of pc_hip_brakedown_code_create: dims, ind_ptr, col_ind, val (Montgomery)."""
+        mats = self.a_mats + self.b_mats
+        dims = [x for mt in mats for x in (mt.n, mt.m, mt.d)]
+        ind_ptr = [x for mt in mats for x in mt.ind_ptr]
+        col_ind = [x for mt in mats for x in mt.col_ind]
+        val = monts(self.curve, [x for mt in mats for x in mt.val])
+        return dims, ind_ptr, col_ind, val
+
+    def upload(self, ctx):
+        return ctx.brakedown_code(self.curve, self.m, self.m_ext, *self.flat())
+
+
+def default_code(curve, num_vars, seed, bits=None):
+    """MultilinearBrakedown::setup (mod.rs:38-54) with Gen(seed) as the RNG: (n rows, Code)."""
+    p = field_p(curve)
+    n, m, a_dims, b_dims, _ = default_shape(1 << num_vars, bits or p.bit_length())
+    gen = Gen(seed)
+    a_mats = [make_mat(*d, gen, p) for d in a_dims]                 # make_all(a_dims) before make_all(b_dims), brakedown.rs:123-124
+    b_mats = [make_mat(*d, gen, p) for d in b_dims]
+    return n, Code(curve, m, a_dims, b_dims, a_mats, b_mats)
+
+
+def base_code(curve, m, m_ext=None):
+    """a_dims empty (m < base_len): the base code alone."""
+    return Code(curve, m, [], [], [], [], m_ext)
+
+
+def ragged_code(curve, seed=0xA66ED):
+    """A hand-built two-level code that no default parameter produces: an empty column, a column that holds every row, one non-zero
+    per row (d = 1), dimensions that are no multiples of 64."""
+    p = field_p(curve)
+    gen = Gen(seed)
+
+    def mat(n, m, d, cols):
+        return SprsMat.new_from_columns(n, m, d, [[(i, gen.nonzero(p)) for i in c] for c in cols])
+    a_dims = [(67, 13, 5), (13, 5, 1)]
+    a0 = [list(range(67)), []] + [[i for i in range(67) if (i * 7 + j) % 6 == 0 or (i + j) % 11 == 0] for j in range(2, 13)]
+    a1 = [[0, 3, 4], [], [1, 2, 5, 6, 7], [8, 9, 10, 11], [12]]                       # every row exactly once: d = 1
+    # b_dims[i].n = end[i] - start[i]; m_ext = sum b.m + sum a.n + b[last].n
+    b_last_n, b_m = 9, [21, 6]
+    m_ext = sum(b_m) + 67 + 13 + b_last_n
+    start, end = [67, 80], [m_ext - 21, m_ext - 27]
+    b_dims = [(end[0] - start[0], 21, 4), (end[1] - start[1], 6, 2)]
+    assert b_dims[1][0] == b_last_n
+    b0 = [list(range(b_dims[0][0])), []] + [[i for i in range(b_dims[0][0]) if (i * 5 + j) % 9 == 0] for j in range(2, 21)]
+    b1 = [[0, 8], [], [1], [2, 3, 4], list(range(9)), [5, 6, 7]]
+    mats = [mat(*a_dims[0], a0), mat(*a_dims[1], a1), mat(*b_dims[0], b0), mat(*b_dims[1], b1)]
+    for mt, (n, _, d) in zip(mats, a_dims + b_dims):
+        assert len(mt.val) <= n * d
+    return Code(curve, 67, a_dims, b_dims, mats[:2], mats[2:])
+
+
+# ---- encode (multilinear_brakedown/mod.rs:56-122) ------------------------------------------------------------------------------------
+def naive_reed_solomon(cw, s, ie, oe, p):
+    res = []
+    for x in range(1, oe - s + 1):
+        r = 0
+        for j in range(ie - 1, s - 1, -1):
+            r = (r * x + cw[j]) % p
+        res.append(r)
+    cw[s:oe] = res
+
+
+def encode(code, msg, b_order=None, clip=False):
+    """MultilinearBrakedown::encode.  b_order: the order of the last loop, default the reference's (level 0 FIRST: mod.rs:79 has no
+    `.rev()`, so level i reads zeros where the levels after it write).  clip: every level uses only the entries whose input position
+    is below end[last] -- the form the device runs, in one launch."""
+    p = code.p
+    assert len(msg) == code.m
+    cw = list(msg)
+    for i, s in enumerate(code.start):
+        cw += code.a_mats[i].row_mul(cw[s - code.a_dims[i][0]:s], p)
+    cw += [0] * (code.m_ext - len(cw))
+    rss = code.start[-1] if code.start else 0
+    rsie = rss + (code.a_dims[-1][1] if code.a_dims else code.m)
+    rsoe = code.end[-1] if code.end else code.m_ext
+    naive_reed_solomon(cw, rss, rsie, rsoe, p)
+    for i in (range(len(code.start)) if b_order is None else b_order):
+        s, e = code.start[i], code.end[i]
+        cw[e:e + code.b_dims[i][1]] = code.b_mats[i].row_mul(cw[s:e], p, clip=(rsoe - s) if clip else None)
+    return cw
+
+
+# ---- MultilinearBrakedown: commit / open / check on canonical integers (linear_codes/mod.rs:228-503) -----------------------------------
+def num_queries(curve, m_ext):
+    return R.calculate_t(field_p(curve).bit_length(), SEC_PARAM, distance(), m_ext)
+
+
+def tensor(curve, point, left_len):
+    """MultilinearBrakedown::tensor (mod.rs:96-107): the point split at log2(left_len)."""
+    return R.ligero_multilinear_tensor(R.CURVES[curve]["fr"], point, left_len)
+
+
+def ref_commit(code, n_rows, evals, col_hash="blake2s", tree_hash="sha256", len_prefix=True):
+    fr = R.CURVES[code.curve]["fr"]
+    flat = list(evals) + [0] * (n_rows * code.m - len(evals))
+    mat = [flat[r * code.m:(r + 1) * code.m] for r in range(n_rows)]
+    ext = [encode(code, row) for row in mat]
+    leaves = [R.column_digest(fr, [ext[r][j] for r in range(n_rows)], col_hash) for j in range(code.m_ext)]
+    nodes = R.merkle_tree(leaves, tree_hash, len_prefix)
+    return dict(n_rows=n_rows, n_cols=code.m, n_ext_cols=code.m_ext, root=nodes[0], mat=mat, ext=ext, leaves=leaves, nodes=nodes)
+
+
+def ref_open(code, st, indices, r, tensors):
+    return R.ligero_open(R.CURVES[code.curve]["fr"], st, None, indices, r, tensors=tensors)
+
+
+def ref_check(code, commitment, value, proof, indices, r, tensors, col_hash="blake2s", tree_hash="sha256"):
+    """LinearCodePCS::check (:375-503); raises InvalidCommitment where the reference returns Err, False for a wrong value."""
+    fr, p = R.CURVES[code.curve]["fr"], code.p
+    n_rows, n_cols, n_ext, t = commitment["n_rows"], commitment["n_cols"], commitment["n_ext_cols"], len(indices)
+    if (r is not None) != (proof["well_formedness"] is not None):
+        raise InvalidCommitment("well-formedness")
+    if (len(proof["columns"]) != t or len(proof["paths"]) != t or len(proof["v"]) != n_cols or any(len(c) != n_rows for c in proof["columns"])
+            or any(not 0 <= i < n_ext for i in indices) or (r is not None and (len(proof["well_formedness"]) != n_cols or len(r) != n_rows))):
+        raise InvalidCommitment("proof shape")
+    for col, q_j, (idx, sib, path) in zip(proof["columns"], indices, proof["paths"]):
+        if idx != q_j or not R.merkle_verify(commitment["root"], R.column_digest(fr, col, col_hash), idx, sib, path, tree_hash):
+            raise InvalidCommitment("path")
+    w = encode(code, proof["v"])
+    a, b = tensors
+    wwf = encode(code, proof["well_formedness"]) if r is not None else None
+    for col, idx in zip(proof["columns"], indices):
+        if r is not None and sum(map(mul, r, col)) % p != wwf[idx]:
+            raise InvalidCommitment("well-formedness inner product")
+        if sum(map(mul, b, col)) % p != w[idx]:
+            raise InvalidCommitment("b . column != w")
+    return sum(map(mul, proof["v"], a)) % p == value % p
+
+
+# ---- the device path -------------------------------------------------------------------------------------------------------------------
+def commit(ctx, code, dev_code, n_rows, evals_dev, col_hash="blake2s", tree_hash="sha256", len_prefix=True):
+    """LinearCodePCS::commit for one polynomial: evals_dev torch cuda int64 (len, 4), Montgomery.  The matrix, the encoded matrix,
+    leaves and nodes stay in the commitment state."""
+    import torch
+    mat = torch.zeros((n_rows * code.m, 4), dtype=torch.int64, device=evals_dev.device)
+    mat[:evals_dev.shape[0]] = evals_dev
+    ext = torch.empty((n_rows * code.m_ext, 4), dtype=torch.int64, device=evals_dev.device)
+    nodes, leaves = dev_code.commit(mat, rows=n_rows, col_hash=col_hash, tree_hash=tree_hash, len_prefix=len_prefix, ext_out=ext)
+    com = dict(n_rows=n_rows, n_cols=code.m, n_ext_cols=code.m_ext, root=bytes(nodes[0]))
+    return com, dict(mat=mat, ext=ext, leaves=leaves, nodes=nodes, **com)
+
+
+def open(ctx, code, state, indices, r_mont, tensors):   # noqa: A001 (the reference's name)
+    from harness import ligero
+    return ligero.open(ctx, code.curve, state, None, indices, r_mont, tensors=tensors)
+
+
+def check(ctx, code, dev_code, commitment, value_mont, proof, indices, r_mont, tensors, col_hash="blake2s", tree_hash="sha256"):
+    from harness import ligero
+    curve, p = code.curve, code.p
+    n_rows, n_cols, n_ext = commitment["n_rows"], commitment["n_cols"], commitment["n_ext_cols"]
+    if (r_mont is not None) != (proof["well_formedness"] is not None):
+        raise InvalidCommitment("well-formedness proof missing or unexpected")
+    indices = [int(i) for i in indices]
+    t = len(indices)
+    try:
+        cols = np.ascontiguousarray(proof["columns"], dtype=np.uint64)
+        v_arr = np.ascontiguousarray(proof["v"], dtype=np.uint64)
+        wf_arr = None if proof["well_formedness"] is None else np.ascontiguousarray(proof["well_formedness"], dtype=np.uint64)
+    except (TypeError, ValueError):
+        raise InvalidCommitment("proof shape")
+    height = max(1, (n_ext - 1).bit_length())
+    if (cols.shape != (t, n_rows, 4) or len(proof["paths"]) != t or v_arr.shape != (n_cols, 4) or (wf_arr is not None and wf_arr.shape != (n_cols, 4))
+            or n_ext != dev_code.codeword_len or n_cols != code.m or any(not 0 <= i < n_ext for i in indices)
+            or any(len(pth) != 3 or len(pth[1]) not in (0, 32) or len(pth[2]) != height - 1 or any(len(s) != 32 for s in pth[2]) for pth in proof["paths"])):
+        raise InvalidCommitment("proof shape")
+    digests = ctx.column_hash(curve, np.ascontiguousarray(cols.transpose(1, 0, 2)), col_hash)
+    for j, (q_j, (idx, sib, path)) in enumerate(zip(indices, proof["paths"])):
+        if idx != q_j or not ligero._merkle_verify(commitment["root"], bytes(digests[j]), idx, sib, path, tree_hash):
+            raise InvalidCommitment(f"path of column {q_j}")
+    # w = E(v) and E(well_formedness): one call, one or two rows
+    msgs = np.ascontiguousarray(np.stack([v_arr] + ([wf_arr] if wf_arr is not None else [])))
+    enc = dev_code.encode(msgs)
+    w = ints(curve, enc[0][indices])
+    a, b = tensors
+    col_ints = [ints(curve, cols[j]) for j in range(t)]
+    if r_mont is not None:
+        wwf, r = ints(curve, enc[1][indices]), ints(curve, r_mont)
+        for j in range(t):
+            if sum(map(mul, r, col_ints[j])) % p != wwf[j]:
+                raise InvalidCommitment(f"well-formedness at column {indices[j]}")
+    for j in range(t):
+        if sum(map(mul, b, col_ints[j])) % p != w[j]:
+            raise InvalidCommitment(f"b.column != w at column {indices[j]}")
+    return sum(map(mul, ints(curve, v_arr), a)) % p == ints(curve, value_mont)[0]
+
+
+# ---- helpers of both test files --------------------------------------------------------------------------------------------------------
+def driver():
+    libdir = os.path.join(ROOT, "poly_commit_amd")
+    if not os.path.exists(os.path.join(libdir, "libpc_hip.so")):
+        import importlib
+        importlib.import_module("poly_commit_amd.build").build()
+    exe = os.path.join(TESTS, "cpp", "brakedown_driver")
+    deps = [exe + ".cpp", os.path.join(libdir, "libpc_hip.so")] + [os.path.join(libdir, "host", h) for h in os.listdir(os.path.join(libdir, "host"))]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
+        tmp = "%s.%d.tmp" % (exe, os.getpid())
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-pthread", "-o", tmp, exe + ".cpp", "-L" + libdir, "-lpc_hip",
+                               "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
+        os.replace(tmp, exe)
+    return exe
+
+
+def flat_arrays(code):
+    dims, ind_ptr, col_ind, val = code.flat()
+    return (np.ascontiguousarray(dims, dtype=np.uintp), np.ascontiguousarray(ind_ptr, dtype=np.uintp), np.ascontiguousarray(col_ind, dtype=np.uint32),
+            np.ascontiguousarray(val, dtype=np.uint64).reshape(-1, 4))
+
+
+def messages(code, rows, seed):
+    g = Gen(seed)
+    return [[g.nonzero(code.p) for _ in range(code.m)] for _ in range(rows)]
+
+
+def malformed(code):
+    """(name, dims, ind_ptr, col_ind, m_ext) of the four broken variants of a valid code."""
+    dims, ind_ptr, col_ind, _ = flat_arrays(code)
+    out = []
+    ip = ind_ptr.copy(); ip[3], ip[4] = ip[4] + 1, ip[3]
+    out.append(("ind_ptr not monotone", dims, ip, col_ind, code.m_ext))
+    ci = col_ind.copy(); ci[len(ci) // 2] = 1 << 30
+    out.append(("col_ind >= n", dims, ind_ptr, ci, code.m_ext))
+    ci = col_ind.copy(); ci[0] = code.a_dims[0][0]
+    out.append(("col_ind == n", dims, ind_ptr, ci, code.m_ext))
+    dm = dims.copy(); dm[3] += 1                                  # a_dims[1].n != a_dims[0].m
+    out.append(("broken chain", dm, ind_ptr, col_ind, code.m_ext))
+    out.append(("wrong codeword_len", dims, ind_ptr, col_ind, code.m_ext + 1))
+    return out
