@@ -12,6 +12,7 @@
 // (poly-commit/src/kzg10/mod.rs:175-178, :209).
 #pragma once
 #include "fp32.hpp"
+#include "fp30.hpp"
 
 namespace pc {
 
@@ -130,6 +131,51 @@ struct XyzzD {
     // x = X / ZZ, y = Y / ZZZ ; one inversion of ZZ*ZZZ
     Fq t = ZZ.mul(ZZZ).inv();
     AffD<C> a; a.x = X.mul(t.mul(ZZZ)); a.y = Y.mul(t.mul(ZZ)); return a;
+  }
+};
+
+
+// The running sum of the BLS12-381 bucket accumulation in radix 2^30 (fp30.hpp): the mixed addition of add_affine_lz, same formulas and
+// special cases, on 13-limb coordinates whose products need no carry instruction.  Invariant between additions (classes of fp30.hpp):
+// X, Y of class 64, ZZ, ZZZ of class 2; infinity is the exact ZZ == 0 (a product ZZ * PP = 0 (mod p) needs P = 0 (mod p), which
+// takes the same-x branch).  The affine operand arrives in the 12-word layout and is converted on the way in; to32() hands the sum
+// back in that layout, lazily reduced, where it leaves the lane.
+struct XyzzR30 {
+  typedef pc_curve_bls12_381 C;
+  typedef Fd<C::FqP> F32;
+  typedef Fq30 Fq;
+  Fq X, Y, ZZ, ZZZ;
+
+  static PC_HD XyzzR30 infinity() { XyzzR30 r; r.X = Fq::zero(); r.Y = Fq::zero(); r.ZZ = Fq::zero(); r.ZZZ = Fq::zero(); return r; }
+  PC_HD bool is_inf() const { return ZZ.is_zero_exact(); }
+  // coordinates below 2p in the 12-word R = 2^384 form: what a lazily reduced XyzzD holds (fp32.hpp LAZY_STORE_OK); ZZ = 0 stays 0
+  PC_HD XyzzD<C> to32() const { XyzzD<C> r; r.X = X.to32(); r.Y = Y.to32(); r.ZZ = ZZ.to32(); r.ZZZ = ZZZ.to32(); return r; }
+  // from canonical 12-word coordinates: X, Y re-cut (class 64), ZZ, ZZZ brought to class 2 by one product each (rare path only)
+  static PC_HD XyzzR30 from32(const XyzzD<C>& p) {
+    XyzzR30 r; r.X = Fq::from32(p.X); r.Y = Fq::from32(p.Y); r.ZZ = Fq::from32(p.ZZ).reduce(); r.ZZZ = Fq::from32(p.ZZZ).reduce(); return r;
+  }
+  PC_HD void add_affine(const AffD<C>& a, bool negate) {
+    if (a.y.is_zero()) { if (a.x.is_zero()) return; }        // infinity = (0, 0), decided on the loaded words
+    const F32 ay32 = negate ? a.y.neg_lz_canonical() : a.y;   // the signed digit's negation on the canonical y: in (0, p]
+    const Fq ax = Fq::from32(a.x), ay = Fq::from32(ay32);    // class 64
+    if (is_inf()) { X = ax; Y = ay; ZZ = Fq::one(); ZZZ = Fq::one(); return; }
+    const Fq U2 = Fq::mul<64, 2>(ax, ZZ), S2 = Fq::mul<64, 2>(ay, ZZZ);           // 128 / 630: class 2
+    const Fq Pp = Fq::sub<64>(U2, X), R = Fq::sub<64>(S2, Y);                     // X, Y <= 64p: class 66
+    if (Pp.is_zero_modp<66>()) {       // same x: the sum IS the base (doubling) or its negative -- the canonical code on the base's 12 words (rare)
+      if (R.is_zero_modp<66>()) { AffD<C> b; b.x = a.x; b.y = ay32.canon(); *this = from32(XyzzD<C>::dbl_affine(b)); }
+      else *this = infinity();
+      return;
+    }
+    const Fq PP = Fq::sqr<66>(Pp);                                                 // 4356 / 630: class 8
+    const Fq PPP = Fq::mul<66, 8>(Pp, PP), Q = Fq::mul<64, 8>(X, PP);             // 528, 512: class 2
+    const Fq RR = Fq::sqr<66>(R);                                                  // class 8
+    const Fq X3 = Fq::sub_dbl<4>(Fq::sub<2>(RR, PPP), Q);                          // RR - PPP + 2p: class 10; - 2Q + 4p: class 14
+    const Fq T = Fq::sub<14>(Q, X3), NY = Fq::neg<64>(Y);                          // class 16, class 64
+    Y = Fq::mul_add_mul<66, 16, 64, 2>(R, T, NY, PPP);                             // R (Q - X3) - Y PPP: (1056 + 128) / 630: class 3
+    X = X3;
+    ZZ = Fq::mul<2, 8>(ZZ, PP); ZZZ = Fq::mul<2, 2>(ZZZ, PPP);                    // class 2
+    static_assert(Fq::mul_out(64 * 2) <= 2 && Fq::mul_out(66 * 66) <= 8 && Fq::mul_out(66 * 8) <= 2 && Fq::mul_out(64 * 8) <= 2, "classes of add_affine");
+    static_assert(Fq::mul_out(66 * 16 + 64 * 2) <= 64 && 8 + 2 + 4 <= 64 && Fq::mul_out(2 * 8) <= 2 && Fq::mul_out(2 * 2) <= 2, "the invariant closes");
   }
 };
 

@@ -293,9 +293,16 @@ PC_HD void partial_slot_range(const uint32_t* offs, uint32_t key, uint32_t T, ui
 // ---------------------------------------------------------------------------------------
 // 4. accumulate: one chunk of T sorted entries per lane
 // ---------------------------------------------------------------------------------------
+// the form of the running sum: radix 2^30 for BLS12-381 (ec.hpp XyzzR30; PC_ACC_R30, fp30.hpp), the 12- / 8-limb XyzzD otherwise
+template <class C> struct AccSum { static constexpr bool R30 = false; typedef XyzzD<C> type; };
+#if PC_ACC_R30
+template <> struct AccSum<pc_curve_bls12_381> { static constexpr bool R30 = true; typedef XyzzR30 type; };
+#endif
 template <class C>
 struct AccumulateBody {
   typedef XyzzD<C> Pt;
+  typedef typename AccSum<C>::type Sum;
+  static constexpr bool R30 = AccSum<C>::R30;
   static constexpr int AW = 2 * Fd<typename C::FqP>::N;   // words per affine base
   MsmGeom g;
   const uint32_t* bases;     // resident SRS, AW words per point
@@ -313,6 +320,8 @@ struct AccumulateBody {
   static constexpr bool LAZY_STORE = LAZY && Pt::Fq::LAZY_STORE_OK;
   // the form in which a running sum leaves the lane (bucket store, partial list, the register copy the in-workgroup joins use)
   static PC_HD Pt store_form(const Pt& acc) { if constexpr (LAZY && !LAZY_STORE) return acc.canonical(); else return acc; }
+  // (radix 2^30: an exact division by 64 per coordinate takes the sum back to 12 words, below 2p -- the LAZY_STORE form)
+  static PC_HD Pt store_form(const XyzzR30& acc) { static_assert(!R30 || LAZY_STORE, "to32() hands over lazily reduced coordinates"); return acc.to32(); }
   PC_HD void flush(const Pt& acc_lz, uint32_t k, bool complete, uint32_t t, bool first, uint32_t& k0, uint32_t& k1) const {
     // (LAZY_STORE: the sum leaves the lane lazily reduced, coordinates in [0, 2p): every consumer -- the joins of k_accumulate, the
     // segmented and the bucket reduction, the host tail -- feeds loaded coordinates into multiplications first (XyzzD::add), or doubles Y
@@ -338,7 +347,7 @@ struct AccumulateBody {
       // ahead so that a boundary costs no dependent load (it is hit on nearly every iteration by some lane)
       uint32_t run_lo = offsets[k], boundary = offsets[k + 1];
       uint32_t next_boundary = offsets[k + 2 <= g.NB ? k + 2 : g.NB];
-      Pt acc = Pt::infinity();
+      Sum acc = Sum::infinity();
       bool first = true;
       uint32_t val = entries[s];
       uint32_t nval = (s + 1 < e) ? entries[s + 1] : val;
@@ -358,7 +367,7 @@ struct AccumulateBody {
         // rides in the prefetch group below (one more 4-byte load per iteration, nearly always the same cached line).
         if (p == boundary) {
           flush(store_form(acc), k, run_lo >= s, t, first, k0, k1);       // its end, p, is inside the chunk
-          first = false; acc = Pt::infinity();
+          first = false; acc = Sum::infinity();
           k++; run_lo = p; boundary = next_boundary;
           while (boundary <= p) { k++; boundary = offsets[k + 1]; }      // empty buckets (rare): all start at p
         }
@@ -372,12 +381,20 @@ struct AccumulateBody {
         const AffD<C> npt = AffD<C>::load(bases + (size_t)(nval & PC_ACC_DEBUG_IDX_MASK) * g.pt_stride);
         const uint32_t nnval = entries[p + 2 < e ? p + 2 : e - 1];
         next_boundary = offsets[k + 2 <= g.NB ? k + 2 : g.NB];
-        if constexpr (LAZY) acc.add_affine_lz(pt, (val >> 31) != 0); else acc.add_affine(pt.neg_if(val >> 31));
+        if constexpr (R30) acc.add_affine(pt, (val >> 31) != 0);
+        else if constexpr (LAZY) acc.add_affine_lz(pt, (val >> 31) != 0); else acc.add_affine(pt.neg_if(val >> 31));
         val = nval; nval = nnval; pt = npt;
       }
-      acc = store_form(acc);
-      flush(acc, k, run_lo >= s && boundary <= e, t, first, k0, k1);
-      last = acc;
+      // (two spellings of the same tail on purpose: the 32-bit forms keep the statement order they had before the radix-2^30 sum existed, so
+      // that a build with PC_ACC_R30=0 stays instruction-identical to it -- the merged form moved two instructions of that kernel)
+      if constexpr (R30) {
+        last = store_form(acc);
+        flush(last, k, run_lo >= s && boundary <= e, t, first, k0, k1);
+      } else {
+        acc = store_form(acc);
+        flush(acc, k, run_lo >= s && boundary <= e, t, first, k0, k1);
+        last = acc;
+      }
     }
   }
   PC_HD void operator()(uint32_t t) const {

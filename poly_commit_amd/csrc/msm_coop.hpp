@@ -180,7 +180,8 @@ __global__ void __launch_bounds__(256) k_bucket_level_coop2(uint32_t K, uint32_t
 #ifndef PC_ACC_WAVES_N8
 #define PC_ACC_WAVES_N8 1
 #endif
-template <class C> struct AccTune { static constexpr int WAVES = Fd<typename C::FqP>::N <= 8 ? PC_ACC_WAVES_N8 : PC_ACC_WAVES_PER_EU; };
+// (the radix-2^30 running sum, msm.hpp AccSum: held to two waves -- left alone the allocator takes 300 registers and one wave)
+template <class C> struct AccTune { static constexpr int WAVES = Fd<typename C::FqP>::N <= 8 ? PC_ACC_WAVES_N8 : (AccSum<C>::R30 && PC_ACC_WAVES_PER_EU < 2) ? 2 : PC_ACC_WAVES_PER_EU; };
 #define PC_ACC_BOUNDS __launch_bounds__(256, AccTune<C>::WAVES)
 template <class C>
 __global__ void PC_ACC_BOUNDS k_accumulate(AccumulateBody<C> b, uint32_t lanes) {

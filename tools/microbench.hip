@@ -42,6 +42,17 @@ __global__ void __launch_bounds__(256) k_fmul(uint32_t* out, int iters) {
   uint32_t r = 0; for (int i = 0; i < P::N; i++) r ^= x.l[i] ^ y.l[i];
   out[t] = r;
 }
+// the radix-2^30 form of the BLS12-381 Fq product (csrc/fp30.hpp: 338 multiply-adds, no carry instruction), same loop as k_fmul;
+// operands of class 2 (lazily reduced: the products' own outputs)
+__global__ void __launch_bounds__(256) k_fmul30(uint32_t* out, int iters) {
+  typedef pc::Fq30 F;
+  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  F x = F::one(), y = F::one();
+  x.l[0] ^= t & 0xffff; y.l[1] ^= (t * 77) & 0xffff;
+  for (int it = 0; it < iters; it++) { x = F::mul<2, 2>(x, y); y = F::mul<2, 2>(y, x); }
+  uint32_t r = 0; for (int i = 0; i < F::N; i++) r ^= x.l[i] ^ y.l[i];
+  out[t] = r;
+}
 template <class P>
 __global__ void __launch_bounds__(256) k_fsqr(uint32_t* out, int iters) {
   typedef pc::Fd<P> F;
@@ -203,6 +214,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))
   uint32_t r = 0; for (int i = 0; i < C::FqP::N; i++) r ^= acc.X.l[i] ^ acc.ZZ.l[i];
   out[t] = r;
 }
+// the same loop with the running sum in radix 2^30 (ec.hpp XyzzR30: what the accumulate kernel runs for BLS12-381 with PC_ACC_R30);
+// the sum goes back to 12 words and is hashed like the loops above, to compare lane by lane
+template <int W>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))) k_madd30_waves(uint32_t* out, const uint32_t* pts, int npts, int iters) {
+  typedef pc_curve_bls12_381 C;
+  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  pc::XyzzR30 acc = pc::XyzzR30::infinity();
+  constexpr int AW = 2 * C::FqP::N;
+  for (int it = 0; it < iters; it++) {
+    pc::AffD<C> p = pc::AffD<C>::load(pts + (size_t)((t * 31 + it) % npts) * AW);
+    acc.add_affine(p, false);
+  }
+  const pc::XyzzD<C> a32 = acc.to32().canonical();
+  uint32_t r = 0; for (int i = 0; i < C::FqP::N; i++) r ^= a32.X.l[i] ^ a32.ZZ.l[i];
+  out[t] = r;
+}
+template <class C> struct HasR30 { static constexpr bool value = false; };
+template <> struct HasR30<pc_curve_bls12_381> { static constexpr bool value = true; };
 template <class C>
 static int bench_madd(const char* name, uint32_t* out, int blocks, int threads) {
   constexpr int FN = C::FqP::N, AW = 2 * FN;
@@ -226,12 +255,32 @@ static int bench_madd(const char* name, uint32_t* out, int blocks, int threads) 
     printf("  lazily reduced %-12s %8.3f ms  %8.2f M madd/s   (differs from the canonical loop on %zu of %zu lanes)\n", name, ms,
            (double)lanes * it / ms * 1e-3, bad, (size_t)lanes);
   }
-  // the kernel's own addition (lazy where allowed) by occupancy
-  { float m2 = timeit([&]() { hipLaunchKernelGGL((k_madd_waves<C, 2>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); });
-    float m3 = timeit([&]() { hipLaunchKernelGGL((k_madd_waves<C, 3>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); });
-    float m4 = timeit([&]() { hipLaunchKernelGGL((k_madd_waves<C, 4>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); });
-    printf("  kernel form %-12s at 2 / 3 / 4 waves per SIMD: %8.2f / %8.2f / %8.2f M madd/s\n", name,
-           (double)lanes * it / m2 * 1e-3, (double)lanes * it / m3 * 1e-3, (double)lanes * it / m4 * 1e-3); }
+  // the kernel's own addition (lazy where allowed) by occupancy.  BLS12-381 has two forms of the running sum, radix 2^32 and radix 2^30
+  // (csrc/fp30.hpp); both loops run here and are compared lane by lane.  The one the accumulate kernel runs (PC_ACC_R30) is the
+  // "kernel form" line bench.py reads; the other one goes on a line that starts differently
+  // (every one of these launches is compared lane by lane with the canonical loop above: a timing of a loop that computes something else is
+  // worth nothing)
+  { const double ops = (double)lanes * it * 1e-3;
+    size_t d32[3] = {0, 0, 0}, d30[3] = {0, 0, 0};
+    auto differing = [&](size_t& n) { if (hipMemcpy(got.data(), out, lanes * 4, hipMemcpyDeviceToHost) != hipSuccess) { n = lanes; return; }
+                                      n = 0; for (size_t i = 0; i < lanes; i++) n += got[i] != ref[i]; };
+    float m2 = timeit([&]() { hipLaunchKernelGGL((k_madd_waves<C, 2>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d32[0]);
+    float m3 = timeit([&]() { hipLaunchKernelGGL((k_madd_waves<C, 3>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d32[1]);
+    float m4 = timeit([&]() { hipLaunchKernelGGL((k_madd_waves<C, 4>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d32[2]);
+    printf("  lanes that differ from the canonical loop at 2 / 3 / 4 waves per SIMD: %zu / %zu / %zu\n", d32[0], d32[1], d32[2]);
+    if constexpr (HasR30<C>::value) {
+      float n2 = timeit([&]() { hipLaunchKernelGGL((k_madd30_waves<2>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d30[0]);
+      float n3 = timeit([&]() { hipLaunchKernelGGL((k_madd30_waves<3>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d30[1]);
+      float n4 = timeit([&]() { hipLaunchKernelGGL((k_madd30_waves<4>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d30[2]);
+      printf("  the same with the sum in radix 2^30, lanes that differ: %zu / %zu / %zu\n", d30[0], d30[1], d30[2]);
+      if (PC_ACC_R30) {
+        printf("  radix-2^32 form %-12s at 2 / 3 / 4 waves per SIMD: %8.2f / %8.2f / %8.2f M madd/s\n", name, ops / m2, ops / m3, ops / m4);
+        m2 = n2; m3 = n3; m4 = n4;
+      } else {
+        printf("  radix-2^30 form %-12s at 2 / 3 / 4 waves per SIMD: %8.2f / %8.2f / %8.2f M madd/s\n", name, ops / n2, ops / n3, ops / n4);
+      }
+    }
+    printf("  kernel form %-12s at 2 / 3 / 4 waves per SIMD: %8.2f / %8.2f / %8.2f M madd/s\n", name, ops / m2, ops / m3, ops / m4); }
   // the ladder of the IPA key fold: Jacobian doubling / Jacobian += affine (bench.py prices EcFoldGlvBody against these two)
   { float md = timeit([&]() { hipLaunchKernelGGL(k_jac_dbl<C>, dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); });
     float ma = timeit([&]() { hipLaunchKernelGGL(k_jac_madd<C>, dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); });
@@ -256,6 +305,8 @@ int main() {
     const int it = 256;
     float ms = timeit([&]() { hipLaunchKernelGGL(k_fmul<pc_bls12_381_fq>, dim3(blocks), dim3(threads), 0, 0, out, it); });
     printf("fmul bls12_381_fq (12 limbs) %8.3f ms  %8.2f G mulmod/s\n", ms, (double)lanes * it * 2 / ms * 1e-6);
+    ms = timeit([&]() { hipLaunchKernelGGL(k_fmul30, dim3(blocks), dim3(threads), 0, 0, out, it); });
+    printf("fmul30 bls12_381_fq (13 x 30 bits) %2.3f ms  %8.2f G mulmod/s\n", ms, (double)lanes * it * 2 / ms * 1e-6);
     ms = timeit([&]() { hipLaunchKernelGGL(k_fmul<pc_bn254_fq>, dim3(blocks), dim3(threads), 0, 0, out, it); });
     printf("fmul bn254_fq (8 limbs)      %8.3f ms  %8.2f G mulmod/s\n", ms, (double)lanes * it * 2 / ms * 1e-6);
     ms = timeit([&]() { hipLaunchKernelGGL(k_fmul<pc_pallas_fq>, dim3(blocks), dim3(threads), 0, 0, out, it); });
