@@ -484,6 +484,49 @@ int pc_hip_fixed_base_batch_mul(pc_ctx* ctx, pc_curve curve, const void* g_xy_ho
 /* Copy `count` resident affine points starting at `offset` back to the host (final_comm_key). */
 int pc_hip_srs_read(pc_ctx* ctx, const pc_srs* srs, size_t offset, size_t count, void* out_xy);
 
+/* ---- G2 of BLS12-381 and MultilinearPC (poly-commit/src/multilinear_pc/mod.rs, the XZZPD19 multilinear KZG scheme) ----
+ * A G2 affine point is x.c0 || x.c1 || y.c0 || y.c1: four Montgomery residues of Fq, 192 bytes -- arkworks' Fp2 { c0, c1 } inside
+ * short_weierstrass::Affine.  Infinity is all-zero (never on the twist y^2 = x^3 + 4(1 + u)); with a larger stride the byte at offset
+ * 192 is arkworks' infinity flag, as for pc_hip_srs_upload.  A pc_g2_srs is a typed handle of its own: no G1 entry point can be
+ * handed a G2 key.  It belongs to its context: counted by pc_hip_ctx_bytes_resident (out[0] and out[5]) and released by
+ * pc_hip_shutdown if the caller has not freed it (the handle then only remains to be freed).  Only PC_CURVE_BLS12_381 is built
+ * (the curve the reference instantiates, multilinear_pc/mod.rs:247): BN254 and Pallas give PC_ERR_UNSUPPORTED.
+ * The G2 MSM is table-free: no window table, no GLV, no captured launch graphs, no host-parts split. */
+typedef struct pc_g2_srs pc_g2_srs;
+/* The residency hook of MultilinearPC::trim (multilinear_pc/mod.rs:91-111: powers_of_h copied by value at :98). */
+int pc_hip_g2_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t n, size_t stride_bytes, pc_mem where,
+                         pc_g2_srs** out);
+void pc_hip_g2_srs_free(pc_g2_srs* srs);
+size_t pc_hip_g2_srs_len(const pc_g2_srs* srs);
+/* out[0] bases, [1] 0, [2] 0, [3] workspace of the key's MSM pipeline (the layout of pc_hip_srs_bytes_resident). */
+int pc_hip_g2_srs_bytes_resident(const pc_g2_srs* srs, size_t out[4]);
+/* out[out_off + b] = in[off + 2b] + in[off + 2b + 1] for b < count, affine, one inversion per batch.  MultilinearPC::open
+ * multiplies BOTH points of a pair by the same scalar (multilinear_pc/mod.rs:158-160: scalars[x] = q[x >> 1]), so the key of
+ * round i can be replaced by its pair sums once, at trim.  in and out may be the same key if the ranges do not overlap. */
+int pc_hip_g2_srs_pair_sums(pc_ctx* ctx, const pc_g2_srs* in, size_t off, size_t count, pc_g2_srs* out, size_t out_off);
+/* Copy `count` points starting at `offset` to the host (192 bytes each). */
+int pc_hip_g2_srs_read(pc_ctx* ctx, const pc_g2_srs* srs, size_t offset, size_t count, void* out_host);
+/* <E::G2 as VariableBaseMSM>::msm_bigint(&bases[base_offset..], scalars).into_affine() (multilinear_pc/mod.rs:162-163), blocking.
+ * min(n, len - base_offset) pairs, as msm_bigint.  out_xy: 192 bytes on the host. */
+int pc_hip_g2_msm(pc_ctx* ctx, const pc_g2_srs* srs, size_t base_offset, const void* scalars, pc_scalar_form form,
+                  pc_mem where, size_t n, void* out_xy, int* out_is_infinity);
+/* Host utilities, no device needed (like pc_hip_points_sum / pc_hip_point_mul): sum of `count` G2 points; scalar (Montgomery
+ * Fr) times one G2 point (the verifier side of multilinear_pc/mod.rs:172-200 handles a few points on the host). */
+int pc_hip_g2_points_sum(pc_curve curve, const void* points, size_t count, void* out_xy);
+int pc_hip_g2_point_mul(pc_curve curve, const void* point, const void* scalar_mont, void* out_xy);
+/* One halving round of MultilinearPC::open (multilinear_pc/mod.rs:153-157) on device-resident Fr vectors (Montgomery):
+ *   q[b] = r_in[2b + 1] - r_in[2b],   r_out[b] = r_in[2b] * (1 - z) + r_in[2b + 1] * z,   b < n_half.
+ * r_out must not overlap r_in (lane b writes what lane b / 2 reads); q may be any other buffer. */
+int pc_hip_ml_fold(pc_ctx* ctx, pc_curve field_of, const void* r_in_dev, size_t n_half, const void* z_host, void* r_out_dev,
+                   void* q_dev);
+/* MultilinearPC::open as one call (multilinear_pc/mod.rs:131-168): nv rounds of fold + G2 MSM.  pair_key: the concatenation, for
+ * i = 0 .. nv-1, of the pair sums of powers_of_h[i] (pc_hip_g2_srs_pair_sums) -- 2^nv - 1 points, round i at offset
+ * 2^nv - 2^(nv-i): the same group elements the reference multiplies, half the additions, bit-identical proofs.
+ * evals: 2^nv Fr (Montgomery), host or device; point_host: nv Fr; proofs_out: nv x 192 bytes on the host, proof i for point[i];
+ * out_is_infinity: nv flags, or NULL.  Rounds of at most PC_HIP_G2_SMALL_ROUND pairs run as one small kernel each. */
+int pc_hip_ml_open(pc_ctx* ctx, const pc_g2_srs* pair_key, const void* evals, pc_mem where, unsigned nv, const void* point_host,
+                   void* proofs_out, int* out_is_infinity);
+
 /* ---- One committer key over several GPUs of a node, driven from one process ----------------
  * The reference has no multi-device path; this is the form a prover that holds ONE CommitterKey needs.  The key is
  * cut into N contiguous chunks, one per device (chunk d also keeps the one power below it, so that commit and open

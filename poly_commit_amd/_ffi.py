@@ -139,6 +139,19 @@ def load_library():
     lib.pc_hip_group_ligero_commit.argtypes = [vp, ip, vp, sz, sz, C.c_uint, ip, ip, ip, vp, vp, vp]
     lib.pc_hip_group_commit_open_async.argtypes = [vp, vp, vp, ip, sz, vp, vp, vp, vp, C.POINTER(vp)]
     lib.pc_hip_group_job_wait.argtypes = [vp, vp]
+    lib.pc_hip_g2_srs_upload.argtypes = [vp, ip, vp, sz, sz, ip, C.POINTER(vp)]
+    lib.pc_hip_g2_srs_free.argtypes = [vp]
+    lib.pc_hip_g2_srs_free.restype = None
+    lib.pc_hip_g2_srs_len.argtypes = [vp]
+    lib.pc_hip_g2_srs_len.restype = sz
+    lib.pc_hip_g2_srs_bytes_resident.argtypes = [vp, C.POINTER(sz)]
+    lib.pc_hip_g2_srs_pair_sums.argtypes = [vp, vp, sz, sz, vp, sz]
+    lib.pc_hip_g2_srs_read.argtypes = [vp, vp, sz, sz, vp]
+    lib.pc_hip_g2_msm.argtypes = [vp, vp, sz, vp, ip, ip, sz, vp, C.POINTER(ip)]
+    lib.pc_hip_g2_points_sum.argtypes = [ip, vp, sz, vp]
+    lib.pc_hip_g2_point_mul.argtypes = [ip, vp, vp, vp]
+    lib.pc_hip_ml_fold.argtypes = [vp, ip, vp, sz, vp, vp, vp]
+    lib.pc_hip_ml_open.argtypes = [vp, vp, vp, ip, C.c_uint, vp, vp, C.POINTER(ip)]
     _lib = lib
     return lib
 
@@ -406,6 +419,14 @@ class Context:
 
     def upload_srs(self, curve, bases, n=None, stride_bytes=0):
         return Srs(self, curve, bases, n, stride_bytes)
+
+    def upload_g2_srs(self, curve, bases, n=None, stride_bytes=0):
+        return G2Srs(self, curve, bases, n, stride_bytes)
+
+    def ml_fold(self, curve, r_in_dev, n_half, z, r_out_dev, q_dev):
+        """One halving round of MultilinearPC::open on device vectors (pc_hip_ml_fold); z: one Montgomery Fr (host)."""
+        z = np.ascontiguousarray(z)
+        self.check(self.lib.pc_hip_ml_fold(self.h, CURVES[curve], r_in_dev, n_half, C.c_void_p(z.ctypes.data), r_out_dev, q_dev))
 
     def brakedown_code(self, curve, msg_len, codeword_len, dims=(), ind_ptr=(), col_ind=(), val=None):
         """Resident Brakedown code (pc_hip_brakedown_code_create) from the caller's sampled matrices."""
@@ -687,6 +708,103 @@ class Srs:
         if n is None:
             n = scalars.shape[0]
         return MsmJob(self, p, where, n, base_offset, montgomery)
+
+
+class G2Srs:
+    """Resident G2 bases (pc_g2_srs): MultilinearPC's powers_of_h, or their pair sums.  Points are 192 bytes, x.c0 || x.c1 || y.c0 || y.c1."""
+
+    def __init__(self, ctx, curve, bases, n=None, stride_bytes=0):
+        self.ctx, self.curve = ctx, curve
+        p, where = _ptr(bases)
+        if n is None:
+            n = bases.shape[0]
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pc_hip_g2_srs_upload(ctx.h, CURVES[curve], p, n, stride_bytes, where, C.byref(h)))
+        self.h, self.n = h, n
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.pc_hip_g2_srs_free(self.h)
+            self.h = None
+
+    def __len__(self):
+        return int(self.ctx.lib.pc_hip_g2_srs_len(self.h))
+
+    def bytes_resident(self):
+        out = (C.c_size_t * 4)()
+        self.ctx.check(self.ctx.lib.pc_hip_g2_srs_bytes_resident(self.h, out))
+        return dict(zip(("bases", "window_tables", "fold_table", "lanes"), [int(x) for x in out]))
+
+    def read(self, offset, count):
+        out = np.zeros((count, 4 * FQ_BYTES[self.curve]), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.pc_hip_g2_srs_read(self.ctx.h, self.h, offset, count, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def pair_sums_into(self, out_key, off, count, out_off):
+        """out_key[out_off + b] = self[off + 2b] + self[off + 2b + 1], b < count (pc_hip_g2_srs_pair_sums)."""
+        self.ctx.check(self.ctx.lib.pc_hip_g2_srs_pair_sums(self.ctx.h, self.h, off, count, out_key.h, out_off))
+
+    def msm(self, scalars, n=None, base_offset=0, montgomery=False):
+        """sum scalars[i] * bases[base_offset + i]; returns (192-byte uint8 array, is_infinity)."""
+        p, where = _ptr(scalars)
+        if n is None:
+            n = scalars.shape[0]
+        out = np.zeros(4 * FQ_BYTES[self.curve], dtype=np.uint8)
+        inf = C.c_int(0)
+        self.ctx.check(self.ctx.lib.pc_hip_g2_msm(self.ctx.h, self.h, base_offset, p,
+                                                  PC_SCALARS_MONTGOMERY if montgomery else PC_SCALARS_CANONICAL,
+                                                  where, n, C.c_void_p(out.ctypes.data), C.byref(inf)))
+        return out, bool(inf.value)
+
+    def ml_open(self, evals, nv, point):
+        """MultilinearPC::open over this pair-sum key (pc_hip_ml_open): evals 2^nv Montgomery Fr (host array or device pointer), point nv
+        Montgomery Fr (host).  Returns (nv x 192 bytes, nv infinity flags)."""
+        p, where = _ptr(evals)
+        point = np.ascontiguousarray(point)
+        out = np.zeros((nv, 4 * FQ_BYTES[self.curve]), dtype=np.uint8)
+        inf = (C.c_int * nv)()
+        self.ctx.check(self.ctx.lib.pc_hip_ml_open(self.ctx.h, self.h, p, where, nv, C.c_void_p(point.ctypes.data), C.c_void_p(out.ctypes.data), inf))
+        return out, [bool(x) for x in inf]
+
+
+def multilinear_pair_key(ctx, curve, powers_of_h):
+    """The pair-sum key of MultilinearPC::open: powers_of_h = nv host arrays (level i: 2^(nv - i) x 192 bytes).  Every level is uploaded,
+    reduced to its pair sums on the device and dropped; the result holds 2^nv - 1 points, round i at offset 2^nv - 2^(nv - i)."""
+    nv = len(powers_of_h)
+    n = 1 << nv
+    key = G2Srs(ctx, curve, np.zeros((n - 1, 4 * FQ_BYTES[curve]), dtype=np.uint8))
+    for i, level in enumerate(powers_of_h):
+        level = np.ascontiguousarray(level)
+        assert level.shape[0] == n >> i
+        lvl = G2Srs(ctx, curve, level)
+        try:
+            lvl.pair_sums_into(key, 0, n >> (i + 1), n - (n >> i))
+        finally:
+            lvl.free()
+    return key
+
+
+def g2_points_sum(curve, points):
+    """Host-side sum of G2 affine points (k x 192 bytes) -> one point."""
+    lib = load_library()
+    points = np.ascontiguousarray(points)
+    out = np.zeros(4 * FQ_BYTES[curve], dtype=np.uint8)
+    rc = lib.pc_hip_g2_points_sum(CURVES[curve], C.c_void_p(points.ctypes.data), points.shape[0], C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise PcHipError(rc, lib.pc_hip_strerror(rc).decode())
+    return out
+
+
+def g2_point_mul(curve, point, scalar_mont):
+    """Host-side k * P for one G2 affine point and one Montgomery-form Fr."""
+    lib = load_library()
+    point = np.ascontiguousarray(point)
+    scalar_mont = np.ascontiguousarray(scalar_mont)
+    out = np.zeros(4 * FQ_BYTES[curve], dtype=np.uint8)
+    rc = lib.pc_hip_g2_point_mul(CURVES[curve], C.c_void_p(point.ctypes.data), C.c_void_p(scalar_mont.ctypes.data), C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise PcHipError(rc, lib.pc_hip_strerror(rc).decode())
+    return out
 
 
 class MsmJob:

@@ -1,0 +1,265 @@
+// C ABI of the gfx950 backend (include/pc_hip.h): G2 keys, the G2 MSM and MultilinearPC's open (multilinear_pc/mod.rs).  This unit also
+// instantiates everything templated on G2 (g2.hpp, MsmPlan<G2Of<C>, HipBackend>): BLS12-381 only.
+#include "abi.hpp"
+#include "hip_backend_msm.hpp"
+#include "g2.hpp"
+
+namespace pc {
+namespace {
+
+typedef G2Of<pc_curve_bls12_381> G2C;
+typedef pc_curve_bls12_381::FrP FrP;
+constexpr int G2_AW = AffD<G2C>::WORDS, G2_XW = XyzzD<G2C>::WORDS, FR_W = FrP::N;
+
+// One blocking, table-free G2 MSM pipeline: plain launches (no captured graphs), host scalars staged whole (no parts)
+struct G2RunnerT : G2Runner {
+  HipBackend& be;
+  MsmPlan<G2C, HipBackend> plan;
+  G2RunnerT(HipBackend& b, size_t n_max, const MsmConfig& cfg) : be(b), plan(b, n_max, cfg) {}
+  void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) override {
+    const uint32_t* sdev = (const uint32_t*)scalars;
+    be.n_ev = 0; be.mark();
+    if (where == PC_MEM_HOST && n) { be.copy_h2d(plan.scalar_staging(), scalars, n * (size_t)FR_W * 4); sdev = plan.scalar_staging(); }
+    plan.run(bases, base_off, sdev, n, from_mont, out_host);
+  }
+};
+
+G2Lane* g2_lane(pc_g2_srs* k) {
+  if (k->lane) return k->lane;
+  G2Lane* L = new G2Lane();
+  try {
+    L->be.init();
+    MsmConfig cfg = k->ctx->msm_cfg;
+    cfg.tbl = nullptr; cfg.tbl_c = 0;
+    cfg.coop2_max_points = 0;      // one lane per point in every cooperative level (the two-lane form splits Fq coordinates)
+    cfg.K1 = 128;                  // a cooperative level's LDS tile: 128 points x 384 bytes = 48 KiB
+    L->runner = new G2RunnerT(L->be, k->n, cfg);
+  } catch (...) { delete L; throw; }
+  k->lane = L;
+  return L;
+}
+
+// the rounds of an opening with at most this many pairs run as one small kernel (k_small_msm) instead of the full pipeline
+uint32_t small_round_max() {
+  static const uint32_t v = []() { const char* e = getenv("PC_HIP_G2_SMALL_ROUND"); int x = e ? atoi(e) : 32; return (uint32_t)(x < 0 ? 0 : x > 128 ? 128 : x); }();
+  return v;
+}
+
+// sum_j k_j P_j for n <= 128 pairs in ONE workgroup: every lane multiplies its pair (ScalarMulBody), a binary tree through LDS adds
+// the products, lane 0 stores the XYZZ sum (the host normalises it: the tail).  blockDim = the power of two >= n, at least 64.
+__global__ void __launch_bounds__(128) k_small_msm(ScalarMulBody<G2C> m, uint32_t n, uint32_t* out_xyzz) {
+  typedef XyzzD<G2C> Pt;
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  LdsPoints<G2C> lds{smem, blockDim.x};
+  const uint32_t l = threadIdx.x;
+  Pt v = l < n ? m.product(l) : Pt::infinity();
+  for (uint32_t d = blockDim.x >> 1; d >= 1; d >>= 1) {
+    lds.put(l, v);
+    __syncthreads();
+    if (l < d) v.add(lds.get(l + d));
+    __syncthreads();
+  }
+  if (l == 0) v.store(out_xyzz);
+}
+
+void small_msm(HipBackend& be, const uint32_t* bases, const uint32_t* scalars_dev, uint32_t n, bool from_mont, uint32_t* out_host) {
+  uint32_t* dres = (uint32_t*)be.workspace((size_t)G2_XW * 4);
+  uint32_t block = 64; while (block < n) block <<= 1;
+  ScalarMulBody<G2C> m{bases, scalars_dev, from_mont ? 1u : 0u};
+  hipLaunchKernelGGL(k_small_msm, dim3(1), dim3(block), (size_t)block * G2_XW * 4, be.stream, m, n, dres);
+  PC_HIP_CHECK(hipGetLastError());
+  uint32_t xyzz[G2_XW];
+  be.copy_d2h(xyzz, dres, sizeof(xyzz));
+  host64::Xyzz64<G2C>::load(xyzz).store_affine(out_host);
+}
+
+}  // namespace
+}  // namespace pc
+
+using pc::G2C;
+using pc::G2_AW;
+using pc::FR_W;
+
+static int g2_curve_check(pc_curve curve) {
+  if ((int)curve < 0 || (int)curve > 2) return PC_ERR_INVALID_ARG;
+  return curve == PC_CURVE_BLS12_381 ? PC_OK : PC_ERR_UNSUPPORTED;
+}
+
+extern "C" {
+
+int pc_hip_g2_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t n, size_t stride_bytes, pc_mem where, pc_g2_srs** out) {
+  if (!ctx || !out || (!bases && n)) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(curve)) return rc;
+  const size_t pb = (size_t)g2_point_bytes(curve);
+  if (stride_bytes == 0) stride_bytes = pb;
+  if (stride_bytes < pb) return PC_ERR_INVALID_ARG;
+  if (n >= (1ull << 31)) return PC_ERR_TOO_LARGE;
+  if (where == PC_MEM_DEVICE && stride_bytes != pb) return PC_ERR_UNSUPPORTED;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  *out = nullptr;
+  pc_g2_srs* k = nullptr;
+  int rc = guarded(ctx, [&]() {
+    k = g2_key_create(ctx, curve, n);
+    if (!k) return (int)PC_ERR_OOM;
+    if (n) {
+      if (where == PC_MEM_DEVICE) ctx->be.copy_d2d(k->bases, bases, n * pb);
+      else if (stride_bytes == pb) ctx->be.copy_h2d(k->bases, bases, n * pb);
+      else {
+        // Rust Affine{x, y, infinity}: repack, mapping the flag to the all-zero encoding
+        std::vector<uint8_t> packed(n * pb);
+        const uint8_t* src = (const uint8_t*)bases;
+        for (size_t i = 0; i < n; i++) {
+          const uint8_t* p = src + i * stride_bytes;
+          if (p[pb]) memset(&packed[i * pb], 0, pb); else memcpy(&packed[i * pb], p, pb);
+        }
+        ctx->be.copy_h2d(k->bases, packed.data(), n * pb);
+        ctx->be.sync();
+      }
+      ctx->be.sync();
+    }
+    return (int)PC_OK;
+  });
+  if (rc != PC_OK) { if (k) g2_key_free(k); return rc; }
+  *out = k;
+  return PC_OK;
+}
+
+void pc_hip_g2_srs_free(pc_g2_srs* k) {
+  if (!k) return;
+  if (k->ctx) { std::lock_guard<std::recursive_mutex> lk(k->ctx->mu); g2_key_free(k); }
+  else g2_key_free(k);
+}
+
+size_t pc_hip_g2_srs_len(const pc_g2_srs* k) { return k ? k->n : 0; }
+
+int pc_hip_g2_srs_bytes_resident(const pc_g2_srs* k, size_t out[4]) {
+  if (!k || !out) return PC_ERR_INVALID_ARG;
+  if (!k->ctx) { out[0] = out[1] = out[2] = out[3] = 0; return PC_OK; }
+  std::lock_guard<std::recursive_mutex> lk(k->ctx->mu);
+  g2_key_bytes(k, out);
+  return PC_OK;
+}
+
+int pc_hip_g2_srs_read(pc_ctx* ctx, const pc_g2_srs* k, size_t offset, size_t count, void* out_host) {
+  if (!ctx || !k || k->ctx != ctx || offset > k->n || count > k->n - offset || (count && !out_host)) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    if (count) ctx->be.copy_d2h(out_host, k->bases + offset * (size_t)k->aw, count * (size_t)k->aw * 4);
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_g2_srs_pair_sums(pc_ctx* ctx, const pc_g2_srs* in, size_t off, size_t count, pc_g2_srs* out, size_t out_off) {
+  if (!ctx || !in || !out || in->ctx != ctx || out->ctx != ctx || in->curve != out->curve) return PC_ERR_INVALID_ARG;
+  if (off > in->n || count > (in->n - off) / 2 || out_off > out->n || count > out->n - out_off) return PC_ERR_INVALID_ARG;
+  if (in == out && off < out_off + count && out_off < off + 2 * count) return PC_ERR_INVALID_ARG;      // overlapping ranges of one key
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    // slabs of 2^17 pairs: 63 MB of workspace (an XYZZ sum and a prefix product per pair) whatever the key's size
+    const size_t SLAB = (size_t)1 << 17;
+    const uint32_t K = 8;
+    for (size_t first = 0; first < count; first += SLAB) {
+      const size_t cnt = std::min(SLAB, count - first);
+      uint32_t* ws = (uint32_t*)ctx->be.workspace(cnt * (size_t)(pc::G2_XW + G2_AW / 2) * 4);
+      pc::PairSumsBody<G2C> b{in->bases + (off + 2 * first) * (size_t)G2_AW, ws, ws + cnt * (size_t)pc::G2_XW,
+                              out->bases + (out_off + first) * (size_t)G2_AW, (uint32_t)cnt, K};
+      ctx->be.launch(b, (cnt + K - 1) / K, 64);
+    }
+    ctx->be.sync();
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_g2_msm(pc_ctx* ctx, const pc_g2_srs* kc, size_t base_offset, const void* scalars, pc_scalar_form form, pc_mem where, size_t n,
+                  void* out_xy, int* out_is_infinity) {
+  pc_g2_srs* k = const_cast<pc_g2_srs*>(kc);
+  if (!ctx || !k || !out_xy || k->ctx != ctx || base_offset > k->n) return PC_ERR_INVALID_ARG;
+  const size_t avail = k->n - base_offset;      // msm_bigint semantics: min(bases.len(), scalars.len()) pairs
+  if (n > avail) n = avail;
+  if (n && !scalars) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    G2Lane* L = pc::g2_lane(k);
+    L->be.timing = ctx->be.timing;
+    L->runner->run(k->bases, (uint32_t)base_offset, scalars, where, n, form == PC_SCALARS_MONTGOMERY, (uint32_t*)out_xy);
+    if (out_is_infinity) *out_is_infinity = affine_is_zero((const uint32_t*)out_xy, G2_AW);
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_g2_points_sum(pc_curve curve, const void* points, size_t count, void* out_xy) {
+  if (!out_xy || (count && !points)) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(curve)) return rc;
+  pc::XyzzD<G2C> acc = pc::XyzzD<G2C>::infinity();
+  for (size_t i = 0; i < count; i++) acc.add_affine(pc::AffD<G2C>::load((const uint32_t*)points + i * G2_AW));
+  acc.to_affine().store((uint32_t*)out_xy);
+  return PC_OK;
+}
+
+int pc_hip_g2_point_mul(pc_curve curve, const void* point, const void* scalar_mont, void* out_xy) {
+  if (!point || !scalar_mont || !out_xy) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(curve)) return rc;
+  typedef pc::host64::Xyzz64<G2C> P64;
+  const uint32_t* pt = (const uint32_t*)point;
+  const pc::Fd<pc::FrP> kk = pc::Fd<pc::FrP>::load((const uint32_t*)scalar_mont).from_mont();
+  P64 base = P64::infinity();
+  if (!affine_is_zero(pt, G2_AW)) { base.X = P64::Fq::load(pt); base.Y = P64::Fq::load(pt + G2_AW / 2); base.ZZ = P64::Fq::one(); base.ZZZ = P64::Fq::one(); }
+  P64 acc = P64::infinity();
+  for (int bit = FR_W * 32 - 1; bit >= 0; bit--) {
+    acc = acc.dbl();
+    if ((kk.l[bit >> 5] >> (bit & 31)) & 1) acc.add(base);
+  }
+  acc.store_affine((uint32_t*)out_xy);
+  return PC_OK;
+}
+
+int pc_hip_ml_fold(pc_ctx* ctx, pc_curve field_of, const void* r_in_dev, size_t n_half, const void* z_host, void* r_out_dev, void* q_dev) {
+  if (!ctx || !z_host || (n_half && (!r_in_dev || !r_out_dev || !q_dev))) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(field_of)) return rc;
+  if (n_half >= (1ull << 31)) return PC_ERR_TOO_LARGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    if (!n_half) return (int)PC_OK;
+    pc::MlFoldBody<pc::FrP> b; b.r_in = (const uint32_t*)r_in_dev; b.r_out = (uint32_t*)r_out_dev; b.q = (uint32_t*)q_dev;
+    memcpy(b.z, z_host, sizeof(b.z));
+    ctx->be.launch(b, n_half);
+    ctx->be.sync();
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_ml_open(pc_ctx* ctx, const pc_g2_srs* kc, const void* evals, pc_mem where, unsigned nv, const void* point_host, void* proofs_out,
+                   int* out_is_infinity) {
+  pc_g2_srs* k = const_cast<pc_g2_srs*>(kc);
+  if (!ctx || !k || k->ctx != ctx || !evals || !point_host || !proofs_out || nv < 1 || nv > 30) return PC_ERR_INVALID_ARG;
+  const size_t n = (size_t)1 << nv;
+  if (k->n != n - 1) return PC_ERR_INVALID_ARG;      // the pair sums of powers_of_h[0 .. nv)
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    const size_t fb = (size_t)FR_W * 4;
+    // r ping-pong (n/2 and n/4 elements; round 0 reads the evaluations where they are, or their staged copy) and q (n/2)
+    Staged ev(ctx->be, evals, where, n * fb, true, 0);
+    CallBuf work(ctx->be, 1, (n / 2 + n / 2 + (n / 4 ? n / 4 : 1)) * fb);
+    uint32_t* q = (uint32_t*)work.dev;
+    uint32_t* rbuf[2] = {q + (n / 2) * FR_W, q + (n / 2 + n / 2) * FR_W};
+    const uint32_t* r_in = (const uint32_t*)ev.dev;
+    G2Lane* L = pc::g2_lane(k);
+    L->be.timing = false;
+    for (unsigned i = 0; i < nv; i++) {
+      const size_t half = n >> (i + 1), off = n - (n >> i);
+      uint32_t* r_out = rbuf[i & 1];
+      pc::MlFoldBody<pc::FrP> b; b.r_in = r_in; b.r_out = r_out; b.q = q;
+      memcpy(b.z, (const uint8_t*)point_host + (size_t)i * fb, sizeof(b.z));
+      ctx->be.launch(b, half);
+      ctx->be.sync();      // the MSM runs on the key's own queue
+      uint32_t* proof = (uint32_t*)proofs_out + (size_t)i * G2_AW;
+      if (half <= pc::small_round_max()) pc::small_msm(ctx->be, k->bases + off * (size_t)G2_AW, q, (uint32_t)half, true, proof);
+      else L->runner->run(k->bases, (uint32_t)off, q, PC_MEM_DEVICE, half, true, proof);
+      if (out_is_infinity) out_is_infinity[i] = affine_is_zero(proof, G2_AW);
+      r_in = r_out;
+    }
+    return (int)PC_OK;
+  });
+}
+
+}  // extern "C"

@@ -13,12 +13,24 @@
 #pragma once
 #include "fp32.hpp"
 #include "fp30.hpp"
+#include "fp2.hpp"
 
 namespace pc {
 
+// The coordinate field of a group: Fq for the curves themselves; Fq2 (fp2.hpp) for G2Of<C>, the group G2 of a pairing curve C on
+// its twist y^2 = x^3 + b' over Fq2 (a = 0 again, so the XYZZ formulas below are the same; b' != 0 keeps (0, 0) off the twist).
+// A G2 affine point is x.c0 || x.c1 || y.c0 || y.c1, arkworks' Affine over Fq2 without the flag; its scalars are C's.
+template <class C1> struct G2Of { typedef C1 Base; typedef typename C1::FqP FqP; typedef typename C1::FrP FrP; };
+template <class C> struct CoordOf { typedef Fd<typename C::FqP> type; };
+template <class C1> struct CoordOf<G2Of<C1>> { typedef Fq2D<typename C1::FqP> type; };
+// the curve whose scalars a group's MSM sorts (the sort stage only looks at scalars)
+template <class C> struct ScalarCurveOf { typedef C type; static constexpr bool IS_G2 = false; };
+template <class C1> struct ScalarCurveOf<G2Of<C1>> { typedef C1 type; static constexpr bool IS_G2 = true; };
+
 template <class C>
 struct AffD {
-  typedef Fd<typename C::FqP> Fq;
+  typedef typename CoordOf<C>::type Fq;
+  static constexpr int WORDS = 2 * Fq::N;
   Fq x, y;
   static PC_HD AffD infinity() { AffD a; a.x = Fq::zero(); a.y = Fq::zero(); return a; }
   PC_HD bool is_inf() const { return x.is_zero() && y.is_zero(); }
@@ -29,7 +41,7 @@ struct AffD {
 
 template <class C>
 struct XyzzD {
-  typedef Fd<typename C::FqP> Fq;
+  typedef typename CoordOf<C>::type Fq;
   static constexpr int WORDS = 4 * Fq::N;
   Fq X, Y, ZZ, ZZZ;
 

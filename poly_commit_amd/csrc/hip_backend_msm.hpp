@@ -66,8 +66,9 @@ void HipBackend::sort_entries(const MsmGeom& g, const uint32_t* scalars, uint32_
 template <class C>
 void HipBackend::accumulate(const AccumulateBody<C>& body, size_t lanes) {
   if (lanes == 0) return;
-  const unsigned wgs = (unsigned)((lanes + 255) / 256);
-  hipLaunchKernelGGL(k_accumulate<C>, dim3(wgs), dim3(256), 0, stream, body, (uint32_t)lanes);
+  constexpr unsigned WG = AccTune<C>::WG;
+  const unsigned wgs = (unsigned)((lanes + WG - 1) / WG);
+  hipLaunchKernelGGL(k_accumulate<C>, dim3(wgs), dim3(WG), 0, stream, body, (uint32_t)lanes);
   PC_HIP_CHECK(hipGetLastError());
   if (wgs > 1) {
     hipLaunchKernelGGL(k_accumulate_edges<C>, dim3((wgs - 1 + 63) / 64), dim3(64), 0, stream, body, (uint32_t)lanes);
@@ -88,10 +89,18 @@ void HipBackend::bucket_level(uint32_t K, uint32_t weight_off, uint32_t cnt, uin
   if (mode) {   // 16 <= K <= 256: one workgroup per group; mode 2: two lanes per point (K <= 128, latency-bound levels)
     uint32_t lgK = 0; while ((1u << lgK) < K) lgK++;
     size_t lds = (size_t)K * XyzzD<C>::WORDS * 4;
-    if (mode == 2 && K <= 128)
-      hipLaunchKernelGGL(k_bucket_level_coop2<C>, dim3(cnt * (1 + n_old)), dim3(2 * K), lds, stream, K, lgK, weight_off, cnt, n_old, x,
-                         old_in, out);
-    else
+    // (the two-lane form splits a point's Fq coordinates over a lane pair: G1 only -- a G2 plan never asks for it, coop2_max_points = 0,
+    // and keeps K <= 128: its tile of K points then fits the 64 KiB a launch may ask for without an attribute)
+    if constexpr (ScalarCurveOf<C>::IS_G2) { if (mode == 2 || K > 128) throw std::runtime_error("bucket_level: G2 levels are one lane per point, K <= 128"); }
+    bool two_lane = false;
+    if constexpr (!ScalarCurveOf<C>::IS_G2) {
+      if (mode == 2 && K <= 128) {
+        two_lane = true;
+        hipLaunchKernelGGL(k_bucket_level_coop2<C>, dim3(cnt * (1 + n_old)), dim3(2 * K), lds, stream, K, lgK, weight_off, cnt, n_old, x,
+                           old_in, out);
+      }
+    }
+    if (!two_lane)
       hipLaunchKernelGGL(k_bucket_level_coop<C>, dim3(cnt * (1 + n_old)), dim3(K), lds, stream, K, lgK, weight_off, cnt, n_old, x,
                          old_in, out);
     PC_HIP_CHECK(hipGetLastError());

@@ -17,6 +17,7 @@ typedef unsigned __int128 u128;
 template <class P>   // P = one of the 32-bit-limb constant structs, N even
 struct F64 {
   static constexpr int N = P::N / 2;
+  static constexpr int WORDS = P::N;      // 32-bit words per element
   uint64_t l[N];
   static constexpr uint64_t mod(int i) { return (uint64_t)P::MOD[2 * i] | ((uint64_t)P::MOD[2 * i + 1] << 32); }
   static constexpr uint64_t inv64() {   // -p^-1 mod 2^64 by Newton iteration
@@ -77,10 +78,44 @@ struct F64 {
   }
 };
 
+// Fq2 = Fq[u] / (u^2 + 1) on the host (the device's Fq2D, fp2.hpp: same layout c0 || c1, same canonical values): the coordinates
+// of the G2 partial sums.  The inversion is (a0 - a1 u) / (a0^2 + a1^2).
+template <class P>
+struct F64x2 {
+  typedef F64<P> F;
+  static constexpr int WORDS = 2 * P::N;
+  F c0, c1;
+  static F64x2 zero() { F64x2 r; r.c0 = F::zero(); r.c1 = F::zero(); return r; }
+  static F64x2 one() { F64x2 r; r.c0 = F::one(); r.c1 = F::zero(); return r; }
+  static F64x2 load(const uint32_t* p) { F64x2 r; r.c0 = F::load(p); r.c1 = F::load(p + P::N); return r; }
+  void store(uint32_t* p) const { c0.store(p); c1.store(p + P::N); }
+  bool is_zero() const { return c0.is_zero() && c1.is_zero(); }
+  F64x2 add(const F64x2& o) const { F64x2 r; r.c0 = c0.add(o.c0); r.c1 = c1.add(o.c1); return r; }
+  F64x2 sub(const F64x2& o) const { F64x2 r; r.c0 = c0.sub(o.c0); r.c1 = c1.sub(o.c1); return r; }
+  F64x2 dbl() const { return add(*this); }
+  F64x2 mul(const F64x2& o) const {      // Karatsuba: 3 products
+    const F v0 = c0.mul(o.c0), v1 = c1.mul(o.c1);
+    F64x2 r; r.c0 = v0.sub(v1); r.c1 = c0.add(c1).mul(o.c0.add(o.c1)).sub(v0).sub(v1);
+    return r;
+  }
+  F64x2 sqr() const { F64x2 r; r.c0 = c0.add(c1).mul(c0.sub(c1)); r.c1 = c0.dbl().mul(c1); return r; }
+  F64x2 inv() const {
+    const F ni = c0.sqr().add(c1.sqr()).inv();
+    F64x2 r; r.c0 = c0.mul(ni); r.c1 = F::zero().sub(c1).mul(ni);
+    return r;
+  }
+};
+
+}  // namespace host64
+template <class C1> struct G2Of;      // ec.hpp
+namespace host64 {
+template <class C> struct Coord64Of { typedef F64<typename C::FqP> type; };
+template <class C1> struct Coord64Of<G2Of<C1>> { typedef F64x2<typename C1::FqP> type; };
+
 template <class C>
 struct Xyzz64 {
-  typedef F64<typename C::FqP> Fq;
-  static constexpr int FW = C::FqP::N;   // 32-bit words per coordinate
+  typedef typename Coord64Of<C>::type Fq;
+  static constexpr int FW = Fq::WORDS;   // 32-bit words per coordinate
   Fq X, Y, ZZ, ZZZ;
   static Xyzz64 infinity() { Xyzz64 r; r.X = r.Y = r.ZZ = r.ZZZ = Fq::zero(); return r; }
   bool is_inf() const { return ZZ.is_zero(); }

@@ -41,6 +41,7 @@ struct pc_ctx {
   std::vector<struct pc_srs*> keys;   // every key object of this context that is alive (pc_hip_ctx_bytes_resident, pc_hip_ctx_trim)
   // pc_hip_ipa_open_rounds: the powers of z, the per-base factors of the fixed key and the two scalar vectors of its rounds (grow-only, pc_hip_ctx_trim frees them)
   void* ipa_buf[3] = {nullptr, nullptr, nullptr}; size_t ipa_bytes[3] = {0, 0, 0};
+  std::vector<struct pc_g2_srs*> g2_keys;   // every G2 key object of this context that is alive (the functions at the end of this header own them)
   std::vector<struct pc_lincode*> codes;   // every Brakedown code object of this context that is alive; abi_lincode.hip alone creates and releases them
   float brakedown_phases[4] = {0, 0, 0, 0};
 };
@@ -411,4 +412,59 @@ inline size_t keys_bytes(const pc_ctx* ctx, size_t out[3]) {
     out[0] += b[0]; out[1] += b[1]; out[2] += b[2];
   }
   return ctx->keys.size();
+}
+
+// ---- G2 keys ---------------------------------------------------------------------------------
+// A key of G2 points (pc_hip_g2_srs_upload; MultilinearPC's powers_of_h and their pair sums): a type of its own, so that no G1 entry
+// point can be handed one.  Same rules as pc_srs: registered in its context, released with it (the host object then stays behind as a
+// tombstone with ctx == nullptr that pc_hip_g2_srs_free only deletes); one pipeline, created on first use by abi_g2.hip.
+struct G2Lane {
+  pc::HipBackend be;
+  pc::G2Runner* runner = nullptr;
+  ~G2Lane() { delete runner; be.destroy(); }
+};
+struct pc_g2_srs {
+  pc_ctx* ctx = nullptr;
+  pc_curve curve = PC_CURVE_BLS12_381;
+  size_t n = 0;
+  uint32_t* bases = nullptr;     // packed x.c0 || x.c1 || y.c0 || y.c1
+  int aw = 0;                    // words per affine point
+  G2Lane* lane = nullptr;
+};
+inline int g2_point_bytes(pc_curve c) { return 4 * fq_bytes(c); }
+
+inline void g2_key_release_device(pc_g2_srs* k) {
+  if (!k->ctx) return;
+  (void)hipSetDevice(k->ctx->device);
+  delete k->lane; k->lane = nullptr;
+  { auto& ks = k->ctx->g2_keys; ks.erase(std::remove(ks.begin(), ks.end(), k), ks.end()); }
+  if (k->bases) k->ctx->be.free(k->bases);
+  k->bases = nullptr; k->n = 0;
+}
+inline void g2_key_free(pc_g2_srs* k) { g2_key_release_device(k); delete k; }
+// call inside guarded(): a failed device allocation throws, with the object already released.  Null: no host memory.
+inline pc_g2_srs* g2_key_create(pc_ctx* ctx, pc_curve curve, size_t n) {
+  pc_g2_srs* k = new (std::nothrow) pc_g2_srs();
+  if (!k) return nullptr;
+  const size_t pb = (size_t)g2_point_bytes(curve);
+  k->ctx = ctx; k->curve = curve; k->n = n; k->aw = (int)(pb / 4);
+  ctx->g2_keys.push_back(k);
+  try { k->bases = (uint32_t*)ctx->be.alloc((n ? n : 1) * pb); }
+  catch (...) { g2_key_free(k); throw; }
+  return k;
+}
+// {bases, 0, 0, pipeline} bytes of one G2 key (the layout of key_bytes: G2 has no tables)
+inline void g2_key_bytes(const pc_g2_srs* k, size_t out[4]) {
+  out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = out[2] = 0;
+  out[3] = k->lane ? k->lane->be.bytes_live : 0;
+}
+// pc_hip_shutdown's share
+inline void g2_keys_shutdown(pc_ctx* ctx) {
+  std::vector<pc_g2_srs*> alive = ctx->g2_keys;
+  for (pc_g2_srs* k : alive) { g2_key_release_device(k); k->ctx = nullptr; }
+  ctx->g2_keys.clear();
+}
+// pc_hip_ctx_trim's share: an idle pipeline gives its sort / scan scratch back
+inline void g2_keys_trim(pc_ctx* ctx) {
+  for (pc_g2_srs* k : ctx->g2_keys) if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }
 }

@@ -55,8 +55,17 @@
     asm volatile("" ::"v"(IDX));                                                                                        \
   } while (0)
 #define PC_ARRIVED_WORD(W) asm volatile("" ::"v"(W))
+// the same for a point over Fq2 (four coefficients per point)
+#define PC_ARRIVED_FQ2(PT, IDX)                                                                                         \
+  do {                                                                                                                  \
+    constexpr int PC_N_ = sizeof((PT).x.c0.l) / 4;                                                                      \
+    for (int pc_i_ = 0; pc_i_ < PC_N_; pc_i_ += 4)                                                                      \
+      asm volatile("" ::"v"((PT).x.c0.l[pc_i_]), "v"((PT).x.c1.l[pc_i_]), "v"((PT).y.c0.l[pc_i_]), "v"((PT).y.c1.l[pc_i_])); \
+    asm volatile("" ::"v"(IDX));                                                                                        \
+  } while (0)
 #else
 #define PC_ARRIVED(PT, IDX) ((void)0)
+#define PC_ARRIVED_FQ2(PT, IDX) ((void)0)
 #define PC_ARRIVED_WORD(W) ((void)0)
 #endif
 
@@ -303,7 +312,7 @@ struct AccumulateBody {
   typedef XyzzD<C> Pt;
   typedef typename AccSum<C>::type Sum;
   static constexpr bool R30 = AccSum<C>::R30;
-  static constexpr int AW = 2 * Fd<typename C::FqP>::N;   // words per affine base
+  static constexpr int AW = AffD<C>::WORDS;   // words per affine base
   MsmGeom g;
   const uint32_t* bases;     // resident SRS, AW words per point
   const uint32_t* entries;
@@ -351,13 +360,16 @@ struct AccumulateBody {
       bool first = true;
       uint32_t val = entries[s];
       uint32_t nval = (s + 1 < e) ? entries[s + 1] : val;
+      // (G2: a 48-word base; holding the next one beside the current one and the 96-word running sum takes the kernel over its 512
+      // registers into scratch -- its bases are loaded where they are used (profiles/EXPERIMENTS.md 0000))
+      constexpr bool PREFETCH_PT = !ScalarCurveOf<C>::IS_G2;
       AffD<C> pt = AffD<C>::load(bases + (size_t)(val & PC_ACC_DEBUG_IDX_MASK) * g.pt_stride);
       for (uint32_t p = s; p < e; p++) {
         // Everything in flight here (the base, the index and the bucket offset gathered during the previous addition) has had a
         // whole addition to arrive: wait for it NOW, before the boundary block below issues its bucket stores.  The memory counter is
         // in order, so the compiler's own wait -- at the first use of `pt`, behind that block -- became vmcnt(0) over the just-issued
         // stores: every wave sat out a store round trip on the iterations in which one of its lanes crosses a bucket boundary.
-        PC_ARRIVED(pt, nval);
+        if constexpr (ScalarCurveOf<C>::IS_G2) PC_ARRIVED_FQ2(pt, nval); else PC_ARRIVED(pt, nval);
         PC_ARRIVED_WORD(next_boundary);
         // Bucket boundary.  NOTHING in this block may wait on memory: some lane of a wave crosses a boundary in 50 % (96 entries per
         // bucket) to 90 % (26) of the iterations.  Until round 4 the look-ahead offsets[k + 2] was loaded HERE -- the compiler
@@ -378,12 +390,20 @@ struct AccumulateBody {
         // the compiler gathered into scratch registers and assembled `npt` from them with copies, i.e. waited for the gather it had
         // just issued -- s_waitcnt vmcnt(3) / vmcnt(2) right behind the four loads of the 8-limb kernels, a memory round trip in
         // EVERY iteration)
+        if constexpr (PREFETCH_PT) {
         const AffD<C> npt = AffD<C>::load(bases + (size_t)(nval & PC_ACC_DEBUG_IDX_MASK) * g.pt_stride);
         const uint32_t nnval = entries[p + 2 < e ? p + 2 : e - 1];
         next_boundary = offsets[k + 2 <= g.NB ? k + 2 : g.NB];
         if constexpr (R30) acc.add_affine(pt, (val >> 31) != 0);
         else if constexpr (LAZY) acc.add_affine_lz(pt, (val >> 31) != 0); else acc.add_affine(pt.neg_if(val >> 31));
         val = nval; nval = nnval; pt = npt;
+        } else {
+          const uint32_t nnval = entries[p + 2 < e ? p + 2 : e - 1];
+          next_boundary = offsets[k + 2 <= g.NB ? k + 2 : g.NB];
+          acc.add_affine(pt.neg_if(val >> 31));
+          val = nval; nval = nnval;
+          pt = AffD<C>::load(bases + (size_t)(val & PC_ACC_DEBUG_IDX_MASK) * g.pt_stride);      // (behind the chunk's end `val` repeats a valid index)
+        }
       }
       // (two spellings of the same tail on purpose: the 32-bit forms keep the statement order they had before the radix-2^30 sum existed, so
       // that a build with PC_ACC_R30=0 stays instruction-identical to it -- the merged form moved two instructions of that kernel)
@@ -471,6 +491,13 @@ struct BucketLevelBody {
     if (a == 0) {
       const uint32_t* base = x + (size_t)gidx * K * Pt::WORDS;
       Pt run = Pt::infinity(), acc = Pt::infinity();
+      // (G2: four 96-word points -- run, acc, cur, nxt -- do not fit the register file: no prefetch there)
+      if constexpr (ScalarCurveOf<C>::IS_G2) {
+        for (uint32_t j = K; j-- > 0;) {
+          run.add(Pt::load(base + (size_t)j * Pt::WORDS));
+          if (j + weight_off > 0) acc.add(run);
+        }
+      } else {
       Pt nxt = Pt::load(base + (size_t)(K - 1) * Pt::WORDS);
       for (uint32_t j = K; j-- > 0;) {
         const Pt cur = nxt;
@@ -478,16 +505,21 @@ struct BucketLevelBody {
         run.add(cur);
         if (j + weight_off > 0) acc.add(run);
       }
+      }
       run.store(out + (size_t)gidx * Pt::WORDS);
       acc.store(out + stride + (size_t)gidx * Pt::WORDS);
     } else {
       const uint32_t* base = old_in + (size_t)(a - 1) * cnt * K * Pt::WORDS + (size_t)gidx * K * Pt::WORDS;
       Pt acc = Pt::infinity();
+      if constexpr (ScalarCurveOf<C>::IS_G2) {
+        for (uint32_t j = 0; j < K; j++) acc.add(Pt::load(base + (size_t)j * Pt::WORDS));
+      } else {
       Pt nxt = Pt::load(base);
       for (uint32_t j = 0; j < K; j++) {
         const Pt cur = nxt;
         nxt = Pt::load(base + (size_t)(j + 1 < K ? j + 1 : j) * Pt::WORDS);
         acc.add(cur);
+      }
       }
       acc.store(out + (size_t)(1 + a) * stride + (size_t)gidx * Pt::WORDS);
     }
@@ -817,12 +849,15 @@ class MsmPlan {
  public:
   typedef XyzzD<C> Pt;
   typedef typename C::FrP FrP;
-  static constexpr int AW = 2 * Fd<typename C::FqP>::N;
+  typedef typename ScalarCurveOf<C>::type SC;      // the sort stage is instantiated for the curve of the scalars (G2: the pairing curve)
+  static constexpr bool G2 = ScalarCurveOf<C>::IS_G2;      // no window table, no GLV split for G2
+  static constexpr int AW = AffD<C>::WORDS;
 
   // subs == 0: one MSM of up to n_max pairs per call.  subs == B > 0: every call is B independent MSMs of
   // n_max / B pairs over the same bases (cfg.tbl must hold their window table); see enqueue().
   MsmPlan(Backend& be, size_t n_max, const MsmConfig& cfg, uint32_t subs = 0) : be_(be), cfg_(cfg), n_max_(n_max), subs_(subs) {
     if (subs_ && (!cfg_.tbl || !cfg_.tbl_c || n_max % subs_)) throw std::runtime_error("MsmPlan: many-MSM mode needs a window table");
+    if (G2 && (subs_ || cfg_.tbl)) throw std::runtime_error("MsmPlan: G2 is table-free");
     if (cfg_.T2 < 4) cfg_.T2 = 4;       // each level must shrink the list: 2*ceil(s/T2) < s
     if (cfg_.T2b < 4) cfg_.T2b = 4;
     // plan_geometry divides the bucket count by these and turns them into Horner exponents: powers of two only
@@ -1015,12 +1050,12 @@ class MsmPlan {
         struct AuxScope { Backend& b; bool marks_was; int* tok; ~AuxScope() { b.timing_marks(marks_was); try { *tok = b.aux_end(); } catch (...) { *tok = -1; } } };
         be_.aux_begin(set_tok_[set], ready_tok);
         AuxScope scope{be_, be_.timing_marks(marks), &tok};
-        be_.template sort_entries<C>(g, scalars_dev, hist, offsets, cursor, entries);
+        be_.template sort_entries<SC>(g, scalars_dev, hist, offsets, cursor, entries);
       }
       be_.wait_token(tok);
     } else {
       // steps 1-3: entries grouped by bucket + CSR offsets (backend chooses the sort)
-      be_.template sort_entries<C>(g, scalars_dev, hist, offsets, cursor, entries);
+      be_.template sort_entries<SC>(g, scalars_dev, hist, offsets, cursor, entries);
     }
 
     { AccumulateBody<C> b{g, g.tbl_stride ? cfg_.tbl : bases_dev, entries, offsets, buckets, pk_[0], pp_[0]}; be_.template accumulate<C>(b, lanes); }
@@ -1103,7 +1138,7 @@ class MsmPlan {
     if (subs_) {      // subs_ affine points: batch-normalise the folded XYZZ results (one inversion in all)
       if (pending_empty_) { for (size_t i = 0; i < (size_t)subs_ * AW; i++) out_host[i] = 0; return; }
       be_.wait_done();
-      if (g_.glv) {      // sub-MSM k = set 2k + phi(set 2k + 1)
+      if constexpr (!G2) if (g_.glv) {      // sub-MSM k = set 2k + phi(set 2k + 1)
         typedef host64::Xyzz64<C> P64;
         std::vector<uint32_t> sum((size_t)subs_ * Pt::WORDS);
         for (uint32_t k = 0; k < subs_; k++) {
@@ -1188,7 +1223,7 @@ class MsmPlan {
     // GLV split: the points of set 1 go through phi -- X * beta in XYZZ coordinates -- before the one Horner chain)
     const uint32_t cw = g_.tbl_stride ? 0u : g_.c;
     const size_t narr = L == 0 ? 1 : arr_exp_.size();
-    if (g_.glv) {
+    if constexpr (!G2) if (g_.glv) {
       typedef host64::Xyzz64<C> P64;
       for (size_t a = 0; a < narr; a++) {
         uint32_t* p = &result_host_[(a * W + 1) * Pt::WORDS];

@@ -181,14 +181,20 @@ __global__ void __launch_bounds__(256) k_bucket_level_coop2(uint32_t K, uint32_t
 #define PC_ACC_WAVES_N8 1
 #endif
 // (the radix-2^30 running sum, msm.hpp AccSum: held to two waves -- left alone the allocator takes 300 registers and one wave)
-template <class C> struct AccTune { static constexpr int WAVES = Fd<typename C::FqP>::N <= 8 ? PC_ACC_WAVES_N8 : (AccSum<C>::R30 && PC_ACC_WAVES_PER_EU < 2) ? 2 : PC_ACC_WAVES_PER_EU; };
-#define PC_ACC_BOUNDS __launch_bounds__(256, AccTune<C>::WAVES)
+// WG: lanes per workgroup.  The exchange tile holds one XYZZ point per lane: 48 KiB at 256 lanes of 12-limb points; a G2 point is twice
+// that (96 words), so G2 runs workgroups of 128 lanes -- the tile stays 48 KiB, the point stays whole
+template <class C> struct AccTune {
+  static constexpr int WAVES = Fd<typename C::FqP>::N <= 8 ? PC_ACC_WAVES_N8 : (AccSum<C>::R30 && PC_ACC_WAVES_PER_EU < 2) ? 2 : PC_ACC_WAVES_PER_EU;
+  static constexpr uint32_t WG = ScalarCurveOf<C>::IS_G2 ? 128u : 256u;
+};
+#define PC_ACC_BOUNDS __launch_bounds__(AccTune<C>::WG, AccTune<C>::WAVES)
 template <class C>
 __global__ void PC_ACC_BOUNDS k_accumulate(AccumulateBody<C> b, uint32_t lanes) {
   typedef XyzzD<C> Pt;
-  __shared__ uint32_t xch[Pt::WORDS * 256];
-  __shared__ uint32_t key_out[256], key_first[256], flags[256];
-  const uint32_t tid = threadIdx.x, t = blockIdx.x * 256 + tid;
+  constexpr uint32_t WG = AccTune<C>::WG;
+  __shared__ uint32_t xch[Pt::WORDS * WG];
+  __shared__ uint32_t key_out[WG], key_first[WG], flags[WG];
+  const uint32_t tid = threadIdx.x, t = blockIdx.x * WG + tid;
   const bool valid = t < lanes;
   uint32_t k0 = KEY_INVALID, k1 = KEY_INVALID;
   Pt V = Pt::infinity();                       // the lane's last run (AccumulateBody::chunk), then the scanned sum of its chain
@@ -202,10 +208,10 @@ __global__ void PC_ACC_BOUNDS k_accumulate(AccumulateBody<C> b, uint32_t lanes) 
   const bool head_right = k0 != KEY_INVALID && k1 == KEY_INVALID && b.offsets[k0 + 1] > ce;   // continues in the next chunk
   const bool transparent = head_left && head_right;
   const uint32_t okey = k1 != KEY_INVALID ? k1 : head_right ? k0 : KEY_INVALID;
-  LdsPoints<C> lds{xch, 256};
+  LdsPoints<C> lds{xch, WG};
   // flags: bit 0 = the sum reaches back to the chain's start (or to lane 0), bit 1 = it stopped at lane 0 without one
   uint32_t fl = (okey == KEY_INVALID || !transparent) ? 1u : 0u;
-  for (uint32_t d = 1; d < 256; d <<= 1) {
+  for (uint32_t d = 1; d < WG; d <<= 1) {
     const bool need = !(fl & 1u);
     if (!__syncthreads_or(need)) break;
     if (okey != KEY_INVALID) lds.put(tid, V);
@@ -221,7 +227,7 @@ __global__ void PC_ACC_BOUNDS k_accumulate(AccumulateBody<C> b, uint32_t lanes) 
   if (okey != KEY_INVALID) lds.put(tid, V);
   __syncthreads();
   const bool take = head_left && tid > 0 && key_out[tid - 1] == k0;
-  const bool give = okey != KEY_INVALID && tid < 255 && key_first[tid + 1] == okey;
+  const bool give = okey != KEY_INVALID && tid < WG - 1 && key_first[tid + 1] == okey;
   if (transparent) {
     // V already holds everything of this bucket from the chain's start (or lane 0) to here
     if (give) k0 = KEY_INVALID;
@@ -251,8 +257,9 @@ template <class C>
 __global__ void __launch_bounds__(64) k_accumulate_edges(AccumulateBody<C> b, uint32_t lanes) {
   PC_LATENCY_KERNEL();
   typedef XyzzD<C> Pt;
+  constexpr uint32_t WG = AccTune<C>::WG;
   const uint32_t k = blockIdx.x * 64 + threadIdx.x;
-  const uint64_t t64 = (uint64_t)(k + 1) * 256;           // first lane of workgroup k + 1
+  const uint64_t t64 = (uint64_t)(k + 1) * WG;            // first lane of workgroup k + 1
   if (t64 >= lanes) return;
   const uint32_t t = (uint32_t)t64, a = t - 1;
   const uint32_t M = b.offsets[b.g.NB];
@@ -278,7 +285,7 @@ __global__ void __launch_bounds__(64) k_accumulate_edges(AccumulateBody<C> b, ui
   b.pkeys[aslot] = KEY_INVALID;
   // complete iff the bucket begins inside the left workgroup (whose scan collected all of it into lane a's piece) and ends
   // inside lane u's chunk
-  const uint64_t ws = (uint64_t)(a - 255u) * b.g.T;
+  const uint64_t ws = (uint64_t)(a - (WG - 1u)) * b.g.T;
   if (b.offsets[key] >= ws && b.offsets[key + 1] <= ue) { f.store(b.buckets + (size_t)key * Pt::WORDS); b.pkeys[2 * u] = KEY_INVALID; }
   else f.store(slot);
 }

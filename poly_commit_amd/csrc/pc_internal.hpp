@@ -36,6 +36,13 @@ struct MsmRunner {
   virtual void trim() = 0;          // give back what can be rebuilt on demand (idle pipeline only)
 };
 
+// One G2 MSM pipeline (abi_g2.hip makes it: MsmPlan<G2Of<C>, HipBackend>, blocking, table-free)
+struct G2Runner {
+  virtual ~G2Runner() {}
+  // out_host: the affine sum, 4 Fq (all zero = infinity)
+  virtual void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) = 0;
+};
+
 struct NttRunner {
   virtual ~NttRunner() {}
   virtual void run(const uint32_t* in, size_t rows, size_t in_cols, uint32_t* out) = 0;
