@@ -2,7 +2,11 @@
 
 The library is split into translation units that compile in parallel (one per curve, one per
 scalar field, the ABI glue, the hash-only kernels); objects are cached under csrc/_obj and
-rebuilt when any source or header is newer."""
+rebuilt when any source or header is newer.
+
+A second target, tests/hip/libpc_probe.so, is test infrastructure: the field and curve primitives of csrc/ one
+per lane (tests/hip/probe_bodies.hpp), for tests/test_device_primitives_gpu.py.  It has its own object cache
+(tests/hip/_obj) and staleness check (its sources and the csrc headers); the product library does not contain it."""
 import concurrent.futures
 import os
 import subprocess
@@ -18,6 +22,14 @@ _VARIANT = os.environ.get("PC_HIP_VARIANT", "")
 OBJ = os.path.join(CSRC, "_obj" + ("_" + _VARIANT if _VARIANT else ""))
 OUT = os.path.join(HERE, "libpc_hip" + ("_" + _VARIANT if _VARIANT else "") + ".so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
+MAX_JOBS = 16
+
+# the probe: (source, PROBE_SET or None); a unit with a set compiles once per curve (tests/hip/probe_sets.hpp)
+PROBE_DIR = os.path.join(os.path.dirname(HERE), "tests", "hip")
+PROBE_OBJ = os.path.join(PROBE_DIR, "_obj")
+PROBE_OUT = os.path.join(PROBE_DIR, "libpc_probe.so")
+PROBE_UNITS = ([("probe_field.hip", k) for k in range(3)] + [("probe_curve.hip", k) for k in range(4)] +
+               [("probe_halfadd.hip", k) for k in range(3)] + [("probe_fq30.hip", None), ("probe_chain30.hip", None)])
 
 
 def _newest_header():
@@ -51,7 +63,63 @@ def needs_build():
     return any(os.path.getmtime(os.path.join(OBJ, s.replace(".hip", ".o"))) > os.path.getmtime(OUT) for s in SOURCES)
 
 
+def _jobs(n):
+    return max(1, min(n, MAX_JOBS, os.cpu_count() or 1))
+
+
+def probe_object(unit):
+    src, k = unit
+    return os.path.join(PROBE_OBJ, src.replace(".hip", "") + ("" if k is None else "_%d" % k) + ".o")
+
+
+def probe_sources():
+    return sorted(os.path.join(PROBE_DIR, f) for f in os.listdir(PROBE_DIR) if f.endswith((".hip", ".hpp")))
+
+
+def _probe_stale_units():
+    src_t = max([_newest_header()] + [os.path.getmtime(f) for f in probe_sources()])
+    return [u for u in PROBE_UNITS if not os.path.exists(probe_object(u)) or os.path.getmtime(probe_object(u)) < src_t]
+
+
+def probe_needs_build():
+    if not os.path.exists(PROBE_OUT) or _probe_stale_units():
+        return True
+    return any(os.path.getmtime(probe_object(u)) > os.path.getmtime(PROBE_OUT) for u in PROBE_UNITS)
+
+
+def build_probe(force=False, verbose=False):
+    """tests/hip/libpc_probe.so for gfx950 (skipped for a PC_HIP_VARIANT build and where the tree has no tests/hip)"""
+    if _VARIANT or not os.path.isdir(PROBE_DIR):
+        return None
+    if not force and not probe_needs_build():
+        return PROBE_OUT
+    os.makedirs(PROBE_OBJ, exist_ok=True)
+    stale = list(PROBE_UNITS) if force else _probe_stale_units()
+
+    def compile_one(unit):
+        src, k = unit
+        cmd = ["hipcc"] + FLAGS + ([] if k is None else ["-DPROBE_SET=%d" % k]) + ["-c", os.path.join(PROBE_DIR, src), "-o", probe_object(unit)]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+
+    with concurrent.futures.ThreadPoolExecutor(max_workers=_jobs(len(stale))) as ex:
+        list(ex.map(compile_one, stale))
+    cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", PROBE_OUT] + [probe_object(u) for u in PROBE_UNITS]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return PROBE_OUT
+
+
 def build(force=False, verbose=False):
+    """both targets; returns the path of the product library"""
+    out = build_product(force, verbose)
+    build_probe(force, verbose)
+    return out
+
+
+def build_product(force=False, verbose=False):
     if not force and not needs_build():
         return OUT
     os.makedirs(OBJ, exist_ok=True)
@@ -68,7 +136,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
         return o
 
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(stale) or 1, os.cpu_count() or 1)) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=_jobs(len(stale))) as ex:
         list(ex.map(compile_one, stale))
     with open(os.path.join(OBJ, "flags.txt"), "w") as f:
         f.write(flags_tag)

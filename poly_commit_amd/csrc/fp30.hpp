@@ -26,7 +26,8 @@
 // no column is listed by hand.
 //
 // Host and device compute the same integers: Montgomery's m is determined by the sum alone, so the host's row-wise form is the
-// device's column-wise one bit for bit (tests/emu steps the real ranges).
+// device's column-wise one bit for bit (tests/emu steps the real ranges; tests/hip runs every instantiation XyzzR30::add_affine makes
+// on the device, on the boundary values of its operand classes: tests/test_device_primitives_gpu.py).
 // (tests/test_emu_cpu.py rebuilds tests/emu/libemu.so when one of the headers it lists is newer; this header is not in that list:
 // remove the library after editing it.)
 #pragma once

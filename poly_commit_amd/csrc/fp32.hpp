@@ -8,7 +8,10 @@
 // (reference call sites: poly-commit/src/kzg10/mod.rs:175-178, :463-470).
 //
 // Everything is PC_HD (host + device) so that the same arithmetic is unit-tested on the CPU
-// (tests/emu) against the independent 64-bit-limb oracle before it ever runs on a GPU.
+// (tests/emu) against the independent 64-bit-limb oracle before it ever runs on a GPU.  The DEVICE forms below (product scanning,
+// the dedicated squaring, the fused pair, their lazy variants) exist in the device compilation only: tests/hip runs each of them
+// one per lane on the boundary operands of its class (tests/test_device_primitives_gpu.py: against Python integers and against the
+// host forms, bit for bit).
 #pragma once
 #include <stdint.h>
 #include "field_constants.h"

@@ -13,11 +13,9 @@ import pytest
 
 import pyref as R
 
+from harness.fq30ref import MASK, N, P, R32, RP, W, class_values, from12, from13, mont, mul_out, normalised, to12, to13
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-P = R.FIELDS["bls12_381_fq"]["p"]
-W, N, MASK = 30, 13, (1 << 30) - 1
-RP = 1 << (W * N)            # R' = 2^390
-R32 = 1 << 384
 _SRC = [os.path.join(HERE, "emu", "emu_fq30.cpp")] + [os.path.join(HERE, "..", "poly_commit_amd", "csrc", f) for f in ("fp30.hpp", "fp32.hpp", "ec.hpp")]
 _libs = {}
 _form = "rows"
@@ -53,25 +51,6 @@ def p32(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
-def to13(v):
-    """an integer as 13 limbs: limbs 0..11 of 30 bits, limb 12 the rest"""
-    assert 0 <= v < 1 << (W * 12 + 32)
-    return np.array([(v >> (W * i)) & MASK for i in range(12)] + [v >> (W * 12)], dtype=np.uint32)
-
-
-def from13(a):
-    return sum(int(x) << (W * i) for i, x in enumerate(a))
-
-
-def to12(v):
-    assert 0 <= v < R32
-    return np.array([(v >> (32 * i)) & 0xffffffff for i in range(12)], dtype=np.uint32)
-
-
-def from12(a):
-    return sum(int(x) << (32 * i) for i, x in enumerate(a))
-
-
 def op(code, *args, n_out=13):
     ins = [a if isinstance(a, np.ndarray) else to13(a) for a in args]
     while len(ins) < 4:
@@ -79,31 +58,6 @@ def op(code, *args, n_out=13):
     out = np.zeros(13, dtype=np.uint32)
     assert lib().fq30_op(code, p32(ins[0]), p32(ins[1]), p32(ins[2]), p32(ins[3]), p32(out)) == 0
     return out[:n_out]
-
-
-def normalised(a):
-    return all(int(x) <= MASK for x in a[:12])
-
-
-def class_values(V, rnd, k=12):
-    """boundary values of class V (integers in [0, V p]) and k random ones; 'all limbs at 2^30 - 1 up to the bound': the largest such
-    value below V p, and the pattern with a zero top limb"""
-    top = (V * P) >> 360
-    ones = (1 << 360) - 1
-    vals = [0, 1, P - 1, P, min(2 * P - 1, V * P), V * P - 1, V * P, ones, ((top - 1) << 360) | ones, (top << 360)]
-    vals += [rnd.randrange(V * P + 1) for _ in range(k)]
-    return [v for v in vals if 0 <= v <= V * P]
-
-
-def mont(ab):
-    """(ab + m p) / R' with m = -ab p^-1 mod R': the exact integer the multiplier returns"""
-    m = (-ab * pow(P, -1, RP)) % RP
-    assert (ab + m * P) % RP == 0
-    return (ab + m * P) // RP
-
-
-def mul_out(prod):
-    return prod // 630 + 2
 
 
 def test_constants():
