@@ -526,6 +526,39 @@ int pc_hip_ml_fold(pc_ctx* ctx, pc_curve field_of, const void* r_in_dev, size_t 
  * out_is_infinity: nv flags, or NULL.  Rounds of at most PC_HIP_G2_SMALL_ROUND pairs run as one small kernel each. */
 int pc_hip_ml_open(pc_ctx* ctx, const pc_g2_srs* pair_key, const void* evals, pc_mem where, unsigned nv, const void* point_host,
                    void* proofs_out, int* out_is_infinity);
+/* MultilinearPC::setup and trim on the device (multilinear_pc/mod.rs:28-86, 91-111).  With the trapdoor t = (t_0 .. t_{nv-1}), level i
+ * (0 <= i < nv) of the parameters is  L_i[x] * g  and  L_i[x] * h  for x < 2^(nv-i),
+ *   L_i[x] = prod_{j = i}^{nv-1} e(t_j, bit_{j-i}(x)),   e(t, 0) = 1 - t,  e(t, 1) = t        (eq_extension, mod.rs:219-234).
+ * L_i[2b] + L_i[2b+1] = L_{i+1}[b] and the sum over the last level is 1: only level 0 is multiplied (2^nv fixed-base multiplications
+ * per group where mod.rs:60-62 does 2^(nv+1) - 2), every higher level is the pair sums of the level below -- the same group elements,
+ * the same canonical bytes.
+ * pc_hip_ml_eq_evals: out_dev[x] = L_0[x], 2^nv Fr (Montgomery in and out; t_host: nv Fr) -- eq_arr[0] of mod.rs:36-51; level i is
+ * the same call on t + i with nv - i.  nv = 1 .. 30. */
+int pc_hip_ml_eq_evals(pc_ctx* ctx, pc_curve field_of, const void* t_host, unsigned nv, void* out_dev);
+/* out[i] = scalars[i] * h for one G2 point h (192 bytes, host; scalars: n Fr, Montgomery, device; out: n x 192 bytes, device):
+ * `h.batch_mul(&pp_powers)`, mod.rs:62 -- the G2 form of pc_hip_fixed_base_batch_mul.  Window table of h (32 x 128 points) built on
+ * the host per call; the results are made and normalised in slabs, so the workspace does not grow with n.  Fewer than 4096 scalars
+ * run a per-lane ladder instead. */
+int pc_hip_g2_fixed_base_batch_mul(pc_ctx* ctx, pc_curve curve, const void* h_host, const void* scalars_dev, size_t n,
+                                   void* out_points_dev);
+/* Address of the resident packed G2 point array (as pc_hip_srs_device_ptr). */
+void* pc_hip_g2_srs_device_ptr(const pc_g2_srs* srs);
+/* UniversalParams of mod.rs:28-86 as two resident keys.  g_xy_host: g (96 bytes), h_host: h (192 bytes), t_host: nv Fr (Montgomery) --
+ * the only parts of a key that cross to the device.  nv = 1 .. 29.
+ *   *out_powers_of_g: 2^(nv+1) - 2 G1 points, level i at offset 2^(nv+1) - 2^(nv-i+1)
+ *   *out_powers_of_h: the same levels of G2 and h itself appended: 2^(nv+1) - 1 points.  (Level i's pair sums are level i + 1 and the
+ *                     last level's pair sum is h, so the key pc_hip_ml_open wants for any supported_num_vars = s is the last 2^s - 1.)
+ *   g_mask_out_host:  nv x 96 bytes, g_mask[i] = t_i * g (mod.rs:75), or NULL.
+ * A level's points for which L_i[x] = 0 (some t_j = 0 or 1) are infinity (all zero).  On failure both outputs are NULL and nothing is
+ * kept.  With pc_hip_set_timing on, pc_hip_last_msm_phases_ms then gives the host-bracketed times of the eq table, G1 level 0, G2
+ * level 0 and the upper levels. */
+int pc_hip_ml_setup(pc_ctx* ctx, pc_curve curve, unsigned nv, const void* g_xy_host, const void* h_host, const void* t_host,
+                    pc_srs** out_powers_of_g, pc_g2_srs** out_powers_of_h, void* g_mask_out_host);
+/* MultilinearPC::trim (mod.rs:91-111) from the resident parameters, device to device: *out_powers_of_g0 = level nv - supported of
+ * powers_of_g (2^supported points, the key of pc_hip_msm for commit), *out_pair_key = the 2^supported - 1 pair sums pc_hip_ml_open
+ * takes.  supported = 1 .. nv; both keys must be those of pc_hip_ml_setup(.., nv, ..) in this context. */
+int pc_hip_ml_trim(pc_ctx* ctx, const pc_srs* powers_of_g, const pc_g2_srs* powers_of_h, unsigned nv, unsigned supported,
+                   pc_srs** out_powers_of_g0, pc_g2_srs** out_pair_key);
 
 /* ---- One committer key over several GPUs of a node, driven from one process ----------------
  * The reference has no multi-device path; this is the form a prover that holds ONE CommitterKey needs.  The key is

@@ -152,6 +152,12 @@ def load_library():
     lib.pc_hip_g2_point_mul.argtypes = [ip, vp, vp, vp]
     lib.pc_hip_ml_fold.argtypes = [vp, ip, vp, sz, vp, vp, vp]
     lib.pc_hip_ml_open.argtypes = [vp, vp, vp, ip, C.c_uint, vp, vp, C.POINTER(ip)]
+    lib.pc_hip_ml_eq_evals.argtypes = [vp, ip, vp, C.c_uint, vp]
+    lib.pc_hip_g2_fixed_base_batch_mul.argtypes = [vp, ip, vp, vp, sz, vp]
+    lib.pc_hip_g2_srs_device_ptr.argtypes = [vp]
+    lib.pc_hip_g2_srs_device_ptr.restype = vp
+    lib.pc_hip_ml_setup.argtypes = [vp, ip, C.c_uint, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
+    lib.pc_hip_ml_trim.argtypes = [vp, vp, vp, C.c_uint, C.c_uint, C.POINTER(vp), C.POINTER(vp)]
     _lib = lib
     return lib
 
@@ -428,6 +434,34 @@ class Context:
         z = np.ascontiguousarray(z)
         self.check(self.lib.pc_hip_ml_fold(self.h, CURVES[curve], r_in_dev, n_half, C.c_void_p(z.ctypes.data), r_out_dev, q_dev))
 
+    def ml_eq_evals(self, curve, t, nv, out_dev):
+        """out_dev[x] = prod_j e(t_j, bit_j(x)), 2^nv Montgomery Fr on the device (pc_hip_ml_eq_evals); t: nv Montgomery Fr (host)."""
+        t = np.ascontiguousarray(t)
+        self.check(self.lib.pc_hip_ml_eq_evals(self.h, CURVES[curve], C.c_void_p(t.ctypes.data), nv, out_dev))
+
+    def g2_fixed_base_batch_mul(self, curve, h_point, scalars_dev, n, out_dev):
+        """out[i] = scalars[i] * h for one G2 point (device buffers): `h.batch_mul` of MultilinearPC::setup."""
+        h_point = np.ascontiguousarray(h_point)
+        self.check(self.lib.pc_hip_g2_fixed_base_batch_mul(self.h, CURVES[curve], C.c_void_p(h_point.ctypes.data), scalars_dev, n, out_dev))
+
+    def ml_setup(self, curve, nv, g, h, t):
+        """MultilinearPC::setup on the device (pc_hip_ml_setup) from g (96 bytes), h (192 bytes) and the trapdoor t (nv Montgomery Fr).
+        Returns (powers_of_g: Srs of 2^(nv+1) - 2 points, powers_of_h: G2Srs of 2^(nv+1) - 1 points with h last, g_mask: nv x 96 bytes);
+        level i of either key starts at ml_level_offset(nv, i)."""
+        g, h, t = np.ascontiguousarray(g), np.ascontiguousarray(h), np.ascontiguousarray(t)
+        mask = np.zeros((nv, 2 * FQ_BYTES[curve]), dtype=np.uint8)
+        hg, hh = C.c_void_p(), C.c_void_p()
+        self.check(self.lib.pc_hip_ml_setup(self.h, CURVES[curve], nv, C.c_void_p(g.ctypes.data), C.c_void_p(h.ctypes.data), C.c_void_p(t.ctypes.data),
+                                            C.byref(hg), C.byref(hh), C.c_void_p(mask.ctypes.data)))
+        return Srs._adopt(self, curve, hg, (2 << nv) - 2), G2Srs._adopt(self, curve, hh, (2 << nv) - 1), mask
+
+    def ml_trim(self, powers_of_g, powers_of_h, nv, supported):
+        """MultilinearPC::trim from resident parameters (pc_hip_ml_trim): (Srs of level nv - supported, 2^supported points; the pair-sum
+        G2Srs of 2^supported - 1 points that ml_open takes)."""
+        hg, hh = C.c_void_p(), C.c_void_p()
+        self.check(self.lib.pc_hip_ml_trim(self.h, powers_of_g.h, powers_of_h.h, nv, supported, C.byref(hg), C.byref(hh)))
+        return Srs._adopt(self, powers_of_g.curve, hg, 1 << supported), G2Srs._adopt(self, powers_of_h.curve, hh, (1 << supported) - 1)
+
     def brakedown_code(self, curve, msg_len, codeword_len, dims=(), ind_ptr=(), col_ind=(), val=None):
         """Resident Brakedown code (pc_hip_brakedown_code_create) from the caller's sampled matrices."""
         return BrakedownCode(self, curve, msg_len, codeword_len, dims, ind_ptr, col_ind, val)
@@ -529,6 +563,13 @@ class Srs:
         else:
             self.ctx.check(self.ctx.lib.pc_hip_srs_precompute_ex(self.ctx.h, self.h, window_bits, min_pairs, 1 if glv else 0))
         return self
+
+    @classmethod
+    def _adopt(cls, ctx, curve, handle, n):
+        """wrap a key the library made (pc_hip_ml_setup, pc_hip_ml_trim)"""
+        out = cls.__new__(cls)
+        out.ctx, out.curve, out.h, out.n = ctx, curve, handle, n
+        return out
 
     def free(self):
         if self.h:
@@ -722,10 +763,21 @@ class G2Srs:
         ctx.check(ctx.lib.pc_hip_g2_srs_upload(ctx.h, CURVES[curve], p, n, stride_bytes, where, C.byref(h)))
         self.h, self.n = h, n
 
+    @classmethod
+    def _adopt(cls, ctx, curve, handle, n):
+        """wrap a key the library made (pc_hip_ml_setup, pc_hip_ml_trim)"""
+        out = cls.__new__(cls)
+        out.ctx, out.curve, out.h, out.n = ctx, curve, handle, n
+        return out
+
     def free(self):
         if self.h:
             self.ctx.lib.pc_hip_g2_srs_free(self.h)
             self.h = None
+
+    def device_ptr(self):
+        """Address of the resident packed point array (pc_hip_g2_srs_device_ptr)."""
+        return int(self.ctx.lib.pc_hip_g2_srs_device_ptr(self.h))
 
     def __len__(self):
         return int(self.ctx.lib.pc_hip_g2_srs_len(self.h))
@@ -765,6 +817,11 @@ class G2Srs:
         inf = (C.c_int * nv)()
         self.ctx.check(self.ctx.lib.pc_hip_ml_open(self.ctx.h, self.h, p, where, nv, C.c_void_p(point.ctypes.data), C.c_void_p(out.ctypes.data), inf))
         return out, [bool(x) for x in inf]
+
+
+def ml_level_offset(nv, i):
+    """points before level i in the keys of Context.ml_setup (level i holds 2^(nv - i) points)"""
+    return (2 << nv) - (2 << (nv - i))
 
 
 def multilinear_pair_key(ctx, curve, powers_of_h):

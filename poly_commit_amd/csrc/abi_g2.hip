@@ -1,12 +1,16 @@
-// C ABI of the gfx950 backend (include/pc_hip.h): G2 keys, the G2 MSM and MultilinearPC's open (multilinear_pc/mod.rs).  This unit also
-// instantiates everything templated on G2 (g2.hpp, MsmPlan<G2Of<C>, HipBackend>): BLS12-381 only.
+// C ABI of the gfx950 backend (include/pc_hip.h): G2 keys, the G2 MSM and MultilinearPC's setup, trim and open (multilinear_pc/mod.rs).
+// This unit also instantiates everything templated on G2 (g2.hpp, the fixed-base bodies of ipa.hpp, MsmPlan<G2Of<C>, HipBackend>):
+// BLS12-381 only.
+#include <chrono>
 #include "abi.hpp"
 #include "hip_backend_msm.hpp"
 #include "g2.hpp"
+#include "ipa.hpp"
 
 namespace pc {
 namespace {
 
+typedef pc_curve_bls12_381 G1C;
 typedef G2Of<pc_curve_bls12_381> G2C;
 typedef pc_curve_bls12_381::FrP FrP;
 constexpr int G2_AW = AffD<G2C>::WORDS, G2_XW = XyzzD<G2C>::WORDS, FR_W = FrP::N;
@@ -73,9 +77,70 @@ void small_msm(HipBackend& be, const uint32_t* bases, const uint32_t* scalars_de
   host64::Xyzz64<G2C>::load(xyzz).store_affine(out_host);
 }
 
+// out[b] = in[2b] + in[2b + 1], b < count, for affine points of G on the device (PairSumsBody).  Slabs of 2^19 pairs: 252 MB of
+// workspace for G2 (an XYZZ sum and a prefix product per pair) whatever the key's size.  A lane adds and normalises K pairs around
+// ONE inversion, and the inversion is most of a lane's run time: K = 8 only where that still leaves 2^16 lanes (one wave on every
+// SIMD; these kernels hold one wave per SIMD for G2), fewer pairs per lane below -- with K = 8 and slabs of 2^17 throughout, every
+// launch was a quarter-filled machine waiting for 16384 serial chains (the upper levels of pc_hip_ml_setup took as long as the 2^nv
+// G2 multiplications of level 0).  `in` and `out` must not overlap.
+template <class G>
+void pair_sums_run(HipBackend& be, const uint32_t* in, size_t count, uint32_t* out) {
+  constexpr int AW = AffD<G>::WORDS, XW = XyzzD<G>::WORDS;
+  const size_t SLAB = (size_t)1 << 19;
+  for (size_t first = 0; first < count; first += SLAB) {
+    const size_t cnt = std::min(SLAB, count - first);
+    const uint32_t K = (uint32_t)std::min<size_t>(8, std::max<size_t>(1, cnt >> 16));
+    uint32_t* ws = (uint32_t*)be.workspace(cnt * (size_t)(XW + AW / 2) * 4);
+    PairSumsBody<G> b{in + 2 * first * (size_t)AW, ws, ws + cnt * (size_t)XW, out + first * (size_t)AW, (uint32_t)cnt, K};
+    be.launch(b, (cnt + K - 1) / K, 64);
+  }
+}
+
+// out[i] = scalars[i] * base, i < n: `base.batch_mul(scalars)` for one affine point of G (host) and n Montgomery scalars on the
+// device; affine results on the device.  What CurveOps::fixed_base does for G1 (curve_ops_impl.hpp), for either group and in slabs:
+// an XYZZ result over Fq2 is 384 bytes, so the results of one slab (2^18: 126 MB with the prefix products) are normalised before the
+// next slab's are made and the workspace does not grow with n.  Below FIXED_BASE_LADDER_BELOW scalars the table (4096 group
+// additions on the host) costs more than it saves: each lane runs its own double-and-add ladder.
+constexpr size_t FIXED_BASE_LADDER_BELOW = 4096, FIXED_BASE_SLAB = (size_t)1 << 18;
+template <class G>
+void fixed_base_run(HipBackend& be, const uint32_t* base, const uint32_t* scalars, size_t n, uint32_t* out) {
+  constexpr int AW = AffD<G>::WORDS, XW = XyzzD<G>::WORDS, FW = AW / 2;
+  if (!n) return;
+  if (n < FIXED_BASE_LADDER_BELOW) {
+    uint32_t* ws = (uint32_t*)be.workspace(((size_t)AW + n * (size_t)(XW + FW)) * 4);
+    uint32_t* dres = ws + AW;
+    be.copy_h2d(ws, base, (size_t)AW * 4);
+    ScalarMulStoreBody<G> body{{ws, scalars, 1u}, dres};
+    be.launch(body, n, 64);
+    XyzzBatchAffineBody<G> nb{dres, dres + n * (size_t)XW, out, (uint32_t)n, 1};
+    be.launch(nb, n, 64);
+    be.sync();
+    return;
+  }
+  // window table of the fixed base on the host: T[w][d-1] = d * 2^(8 w) * base, d = 1..128 (one inversion for all of it)
+  const uint32_t Wd = msm_num_windows(G::FrP::BITS, FIXED_BASE_C);
+  std::vector<uint32_t> tbl;
+  host64::fixed_base_window_table<G>(base, FIXED_BASE_C, Wd, tbl);
+  // device: table | XYZZ results of one slab | their prefix products
+  const size_t slab = std::min(n, FIXED_BASE_SLAB), tb = tbl.size() * 4;
+  uint8_t* ws = (uint8_t*)be.workspace(tb + slab * (size_t)(XW + FW) * 4);
+  uint32_t* dtbl = (uint32_t*)ws; uint32_t* dres = (uint32_t*)(ws + tb); uint32_t* dscr = dres + slab * (size_t)XW;
+  be.copy_h2d(dtbl, tbl.data(), tb);
+  const uint32_t K = 8;
+  for (size_t first = 0; first < n; first += slab) {
+    const size_t cnt = std::min(slab, n - first);
+    FixedBaseTableMulBody<G> body{scalars + first * (size_t)FR_W, dtbl, Wd, dres};
+    be.launch(body, cnt, 64);
+    XyzzBatchAffineBody<G> nb{dres, dscr, out + first * (size_t)AW, (uint32_t)cnt, K};
+    be.launch(nb, (cnt + K - 1) / K, 64);
+  }
+  be.sync();                                   // the host table goes out of scope
+}
+
 }  // namespace
 }  // namespace pc
 
+using pc::G1C;
 using pc::G2C;
 using pc::G2_AW;
 using pc::FR_W;
@@ -155,19 +220,123 @@ int pc_hip_g2_srs_pair_sums(pc_ctx* ctx, const pc_g2_srs* in, size_t off, size_t
   if (in == out && off < out_off + count && out_off < off + 2 * count) return PC_ERR_INVALID_ARG;      // overlapping ranges of one key
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
-    // slabs of 2^17 pairs: 63 MB of workspace (an XYZZ sum and a prefix product per pair) whatever the key's size
-    const size_t SLAB = (size_t)1 << 17;
-    const uint32_t K = 8;
-    for (size_t first = 0; first < count; first += SLAB) {
-      const size_t cnt = std::min(SLAB, count - first);
-      uint32_t* ws = (uint32_t*)ctx->be.workspace(cnt * (size_t)(pc::G2_XW + G2_AW / 2) * 4);
-      pc::PairSumsBody<G2C> b{in->bases + (off + 2 * first) * (size_t)G2_AW, ws, ws + cnt * (size_t)pc::G2_XW,
-                              out->bases + (out_off + first) * (size_t)G2_AW, (uint32_t)cnt, K};
-      ctx->be.launch(b, (cnt + K - 1) / K, 64);
-    }
+    pc::pair_sums_run<G2C>(ctx->be, in->bases + off * (size_t)G2_AW, count, out->bases + out_off * (size_t)G2_AW);
     ctx->be.sync();
     return (int)PC_OK;
   });
+}
+
+void* pc_hip_g2_srs_device_ptr(const pc_g2_srs* k) { return k ? k->bases : nullptr; }
+
+int pc_hip_ml_eq_evals(pc_ctx* ctx, pc_curve field_of, const void* t_host, unsigned nv, void* out_dev) {
+  if (!ctx || !t_host || !out_dev || nv < 1) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(field_of)) return rc;
+  if (nv > pc::ML_MAX_VARS) return PC_ERR_TOO_LARGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    pc::MlEqBody<pc::FrP> b; b.out = (uint32_t*)out_dev; b.set_point((const uint32_t*)t_host, nv);
+    ctx->be.launch(b, (size_t)1 << nv);
+    ctx->be.sync();
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_g2_fixed_base_batch_mul(pc_ctx* ctx, pc_curve curve, const void* h_host, const void* scalars_dev, size_t n, void* out_points_dev) {
+  if (!ctx || !h_host || (n && (!scalars_dev || !out_points_dev))) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(curve)) return rc;
+  if (n >= (1ull << 31)) return PC_ERR_TOO_LARGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    pc::fixed_base_run<G2C>(ctx->be, (const uint32_t*)h_host, (const uint32_t*)scalars_dev, n, (uint32_t*)out_points_dev);
+    return (int)PC_OK;
+  });
+}
+
+// points before level i of a key whose level 0 holds 2^nv points: 2^(nv+1) - 2^(nv-i+1)
+static size_t ml_level_off(unsigned nv, unsigned i) { return ((size_t)2 << nv) - ((size_t)2 << (nv - i)); }
+
+int pc_hip_ml_setup(pc_ctx* ctx, pc_curve curve, unsigned nv, const void* g_xy_host, const void* h_host, const void* t_host,
+                    pc_srs** out_powers_of_g, pc_g2_srs** out_powers_of_h, void* g_mask_out_host) {
+  if (!ctx || !g_xy_host || !h_host || !t_host || !out_powers_of_g || !out_powers_of_h || nv < 1) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(curve)) return rc;
+  if (nv > 29) return PC_ERR_TOO_LARGE;      // a key holds fewer than 2^31 points
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  *out_powers_of_g = nullptr; *out_powers_of_h = nullptr;
+  pc_srs* G = nullptr; pc_g2_srs* H = nullptr;
+  const size_t n0 = (size_t)1 << nv;
+  constexpr int G1_AW = pc::AffD<G1C>::WORDS;
+  int rc = guarded(ctx, [&]() {
+    G = key_create(ctx, curve, 2 * n0 - 2);
+    if (!G) return (int)PC_ERR_OOM;
+    H = g2_key_create(ctx, curve, 2 * n0 - 1);
+    if (!H) return (int)PC_ERR_OOM;
+    pc::HipBackend& be = ctx->be;
+    // with timing on (pc_hip_set_timing) the four phases are bracketed on the host and left where pc_hip_last_msm_phases_ms reads
+    // them: eq table, G1 level 0, G2 level 0, the upper levels
+    const bool timed = be.timing;
+    auto t_prev = std::chrono::steady_clock::now();
+    int phase = 0;
+    auto bracket = [&]() {
+      if (!timed) return;
+      be.sync();
+      const auto now = std::chrono::steady_clock::now();
+      ctx->phases[phase++] = std::chrono::duration<float, std::milli>(now - t_prev).count();
+      t_prev = now;
+    };
+    if (timed) for (int i = 0; i < 8; i++) ctx->phases[i] = 0;
+    // L_0[x] = prod_j e(t_j, bit_j(x)): the only level that is multiplied (mod.rs:36-62 multiplies all 2^(nv+1) - 2 scalars)
+    CallBuf eq(be, 0, n0 * (size_t)FR_W * 4);
+    pc::MlEqBody<pc::FrP> eb; eb.out = (uint32_t*)eq.dev; eb.set_point((const uint32_t*)t_host, nv);
+    be.launch(eb, n0);
+    bracket();
+    pc::fixed_base_run<G1C>(be, (const uint32_t*)g_xy_host, (const uint32_t*)eq.dev, n0, G->bases);
+    bracket();
+    pc::fixed_base_run<G2C>(be, (const uint32_t*)h_host, (const uint32_t*)eq.dev, n0, H->bases);
+    bracket();
+    // L_i[2b] + L_i[2b + 1] = L_{i+1}[b]: every higher level is the pair sums of the one below; the sum of the last one is 1
+    for (unsigned i = 0; i + 1 < nv; i++) {
+      const size_t off = ml_level_off(nv, i), m = n0 >> i;
+      pc::pair_sums_run<G1C>(be, G->bases + off * G1_AW, m / 2, G->bases + (off + m) * G1_AW);
+      pc::pair_sums_run<G2C>(be, H->bases + off * G2_AW, m / 2, H->bases + (off + m) * G2_AW);
+    }
+    be.copy_h2d(H->bases + (2 * n0 - 2) * G2_AW, h_host, (size_t)G2_AW * 4);
+    be.sync();
+    bracket();
+    if (g_mask_out_host)      // g_mask[i] = t_i * g (mod.rs:75): nv multiplications, on the host
+      for (unsigned i = 0; i < nv; i++)
+        pc::curve_ops(curve).point_mul((const uint32_t*)g_xy_host, (const uint32_t*)t_host + (size_t)i * FR_W, (uint32_t*)g_mask_out_host + (size_t)i * G1_AW);
+    return (int)PC_OK;
+  });
+  if (rc != PC_OK) { if (G) key_free(G); if (H) g2_key_free(H); return rc; }
+  *out_powers_of_g = G; *out_powers_of_h = H;
+  return PC_OK;
+}
+
+int pc_hip_ml_trim(pc_ctx* ctx, const pc_srs* powers_of_g, const pc_g2_srs* powers_of_h, unsigned nv, unsigned supported,
+                   pc_srs** out_powers_of_g0, pc_g2_srs** out_pair_key) {
+  if (!ctx || !powers_of_g || !powers_of_h || !out_powers_of_g0 || !out_pair_key) return PC_ERR_INVALID_ARG;
+  if (powers_of_g->ctx != ctx || powers_of_h->ctx != ctx || nv < 1 || supported < 1 || supported > nv) return PC_ERR_INVALID_ARG;
+  if (int rc = g2_curve_check(powers_of_g->curve)) return rc;
+  if (nv > 29) return PC_ERR_TOO_LARGE;
+  if (powers_of_g->n != ((size_t)2 << nv) - 2 || powers_of_h->n != ((size_t)2 << nv) - 1) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  *out_powers_of_g0 = nullptr; *out_pair_key = nullptr;
+  pc_srs* G = nullptr; pc_g2_srs* H = nullptr;
+  const size_t n = (size_t)1 << supported;
+  int rc = guarded(ctx, [&]() {
+    G = key_create(ctx, powers_of_g->curve, n);
+    if (!G) return (int)PC_ERR_OOM;
+    H = g2_key_create(ctx, powers_of_h->curve, n - 1);
+    if (!H) return (int)PC_ERR_OOM;
+    // level nv - supported of G1; the pair sums of the G2 levels [nv - supported, nv) are the levels above them and h: the key's tail
+    ctx->be.copy_d2d(G->bases, powers_of_g->bases + ml_level_off(nv, nv - supported) * (size_t)G->aw, n * (size_t)G->aw * 4);
+    ctx->be.copy_d2d(H->bases, powers_of_h->bases + (powers_of_h->n - (n - 1)) * (size_t)G2_AW, (n - 1) * (size_t)G2_AW * 4);
+    ctx->be.sync();
+    return (int)PC_OK;
+  });
+  if (rc != PC_OK) { if (G) key_free(G); if (H) g2_key_free(H); return rc; }
+  *out_powers_of_g0 = G; *out_pair_key = H;
+  return PC_OK;
 }
 
 int pc_hip_g2_msm(pc_ctx* ctx, const pc_g2_srs* kc, size_t base_offset, const void* scalars, pc_scalar_form form, pc_mem where, size_t n,

@@ -66,6 +66,32 @@ struct MlFoldBody {
   }
 };
 
+// The eq table of MultilinearPC::setup (eq_extension and the running products of mod.rs:36-51, 219-234), Montgomery in and out:
+//   out[x] = prod_{j < nv} e(t_j, bit_j(x)),   e(t, 0) = 1 - t,  e(t, 1) = t
+// one lane per x; both factors of every variable travel in the body (2 x 30 x 8 words).  Level i of the reference's eq_arr is the
+// same table over t[i ..]; out[2b] + out[2b + 1] is the table of t[1 ..] at b.
+static constexpr uint32_t ML_MAX_VARS = 30;
+template <class FrP>
+struct MlEqBody {
+  typedef Fd<FrP> Fr;
+  uint32_t* out;
+  uint32_t nv;
+  uint32_t e[ML_MAX_VARS][2][FrP::N];      // e[j][b] = e(t_j, b)
+  void set_point(const uint32_t* t_mont, uint32_t n_vars) {
+    nv = n_vars;
+    for (uint32_t j = 0; j < n_vars; j++) {
+      const Fr tj = Fr::load(t_mont + (size_t)j * FrP::N);
+      Fr::one().sub(tj).store(e[j][0]); tj.store(e[j][1]);
+    }
+  }
+  PC_HD void operator()(uint32_t x) const {
+    // (both factors are loaded with wave-uniform addresses and selected per lane)
+    Fr acc = fq_sel((x & 1) != 0, Fr::load(e[0][1]), Fr::load(e[0][0]));
+    for (uint32_t j = 1; j < nv; j++) acc = acc.mul(fq_sel(((x >> j) & 1) != 0, Fr::load(e[j][1]), Fr::load(e[j][0])));
+    acc.store(out + (size_t)x * FrP::N);
+  }
+};
+
 // k * P for one lane: the late rounds of an opening (a handful of pairs) are launch-latency bound in the full pipeline, so each lane
 // multiplies its own pair by double-and-add from the top bit (XYZZ) and a workgroup tree adds the products (abi_g2.hip).
 template <class G>
@@ -89,6 +115,19 @@ struct ScalarMulBody {
       if (top) acc.add_affine(p);
     }
     return acc;
+  }
+};
+
+// The same ladder with the product stored: a fixed-base multiplication of a handful of scalars (no window table to build), one base
+// for every lane; normalised by XyzzBatchAffineBody.
+template <class G>
+struct ScalarMulStoreBody {
+  ScalarMulBody<G> m;        // bases: ONE affine point
+  uint32_t* out_xyzz;
+  PC_HD void operator()(uint32_t j) const {
+    ScalarMulBody<G> one = m;
+    one.scalars = m.scalars + (size_t)j * G::FrP::N;
+    one.product(0).store(out_xyzz + (size_t)j * XyzzD<G>::WORDS);
   }
 };
 }  // namespace pc

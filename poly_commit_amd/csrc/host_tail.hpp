@@ -190,5 +190,26 @@ void batch_to_affine(const uint32_t* xyzz, size_t count, uint32_t* out_affine) {
   }
 }
 
+// Window table of one fixed base (affine, 2 * FW words; all zero: infinity) for signed radix-2^c digits:
+//   tbl[w * 2^(c-1) + d - 1] = d * 2^(c w) * base,  d = 1 .. 2^(c-1),  w < Wd      (affine, one inversion for all of it)
+// what FixedBaseTableMulBody (ipa.hpp) reads; G is a curve or G2Of<curve>.
+template <class G>
+void fixed_base_window_table(const uint32_t* base, uint32_t c, uint32_t Wd, std::vector<uint32_t>& tbl) {
+  typedef Xyzz64<G> P;
+  constexpr int FW = P::FW;
+  const uint32_t half = 1u << (c - 1);
+  std::vector<uint32_t> xyzz((size_t)Wd * half * 4 * FW);
+  tbl.assign((size_t)Wd * half * 2 * FW, 0);
+  P b = P::infinity();
+  bool inf = true; for (int i = 0; i < 2 * FW; i++) inf &= base[i] == 0;
+  if (!inf) { b.X = P::Fq::load(base); b.Y = P::Fq::load(base + FW); b.ZZ = P::Fq::one(); b.ZZZ = P::Fq::one(); }
+  for (uint32_t w = 0; w < Wd; w++) {
+    P cur = b;
+    for (uint32_t d = 0; d < half; d++) { cur.store(&xyzz[((size_t)w * half + d) * 4 * FW]); cur.add(b); }
+    for (uint32_t k = 0; k < c; k++) b = b.dbl();
+  }
+  batch_to_affine<G>(xyzz.data(), (size_t)Wd * half, tbl.data());
+}
+
 }  // namespace host64
 }  // namespace pc

@@ -207,36 +207,59 @@ struct FixedBaseMulBody {
 // signed radix-256 recoding -- no doublings: ~320 field products instead of ~2900 for the per-lane NAF ladder.  The table
 // (4096 affine points, 393 KB for BLS12-381) is built on the host per call and read through L2.  Results stay in XYZZ
 // and are normalised by XyzzBatchAffineBody with one inversion per K points.
+// C is a curve or G2Of<curve> (`h.batch_mul` of MultilinearPC::setup, multilinear_pc/mod.rs:62: coordinates over Fq2, 768 KB of table).
 static constexpr uint32_t FIXED_BASE_C = 8;
 template <class C>
 struct FixedBaseTableMulBody {
   typedef Fd<typename C::FrP> Fr;
-  static constexpr int AW = 2 * Fd<typename C::FqP>::N;
+  static constexpr int AW = AffD<C>::WORDS;
   const uint32_t* scalars;   // n x Fr, Montgomery
   const uint32_t* table;     // Wd x 128 affine points
   uint32_t Wd;
   uint32_t* out_xyzz;        // n x XyzzD::WORDS
   PC_HD void operator()(uint32_t i) const {
-    ScalarDigits<typename C::FrP> sd; sd.load(scalars + (size_t)i * C::FrP::N, true);
-    XyzzD<C> acc = XyzzD<C>::infinity();
-    uint32_t carry = 0;
-    const uint32_t half = 1u << (FIXED_BASE_C - 1);
-    sd.for_each_window(FIXED_BASE_C, Wd, [&](uint32_t w, uint32_t bits) {
-      uint32_t raw = bits + carry;
-      carry = raw > half;
-      const uint32_t mag = carry ? (2 * half - raw) : raw;
-      if (mag) acc.add_affine(AffD<C>::load(table + ((size_t)w * half + (mag - 1)) * AW).neg_if(carry != 0));
-    });
-    acc.store(out_xyzz + (size_t)i * XyzzD<C>::WORDS);
+    if constexpr (!ScalarCurveOf<C>::IS_G2) {
+      ScalarDigits<typename C::FrP> sd; sd.load(scalars + (size_t)i * C::FrP::N, true);
+      XyzzD<C> acc = XyzzD<C>::infinity();
+      uint32_t carry = 0;
+      const uint32_t half = 1u << (FIXED_BASE_C - 1);
+      sd.for_each_window(FIXED_BASE_C, Wd, [&](uint32_t w, uint32_t bits) {
+        uint32_t raw = bits + carry;
+        carry = raw > half;
+        const uint32_t mag = carry ? (2 * half - raw) : raw;
+        if (mag) acc.add_affine(AffD<C>::load(table + ((size_t)w * half + (mag - 1)) * AW).neg_if(carry != 0));
+      });
+      acc.store(out_xyzz + (size_t)i * XyzzD<C>::WORDS);
+    } else {
+      // G2: the sum is 96 words and the operand 48, and they must stay in registers.  for_each_window calls its functor at two
+      // sites (the limb loop and the short top windows); a functor holding a whole mixed addition is then not inlined and the sum it
+      // captures by reference lives in scratch memory (464 bytes per lane).  Here the scalar is shifted out a byte at a time with
+      // compile-time limb indices and the addition has ONE call site.  (The G1 form above is the code as it was, statement for
+      // statement: its kernels compile to the instructions they had.)
+      static_assert(FIXED_BASE_C == 8, "the byte walk below");
+      Fr k = Fr::load(scalars + (size_t)i * C::FrP::N).from_mont();
+      XyzzD<C> acc = XyzzD<C>::infinity();
+      uint32_t carry = 0;
+      const uint32_t half = 1u << (FIXED_BASE_C - 1);
+      for (uint32_t w = 0; w < Wd; w++) {
+        const uint32_t raw = (k.l[0] & 0xffu) + carry;
+        PC_UNROLL for (int j = 0; j + 1 < C::FrP::N; j++) k.l[j] = (k.l[j] >> 8) | (k.l[j + 1] << 24);
+        k.l[C::FrP::N - 1] >>= 8;
+        carry = raw > half;
+        const uint32_t mag = carry ? (2 * half - raw) : raw;
+        if (mag) acc.add_affine(AffD<C>::load(table + ((size_t)w * half + (mag - 1)) * AW).neg_if(carry != 0));
+      }
+      acc.store(out_xyzz + (size_t)i * XyzzD<C>::WORDS);
+    }
   }
 };
 
 // XYZZ -> affine for n points, one inversion per K points (Montgomery's trick along a lane's run; x = X / ZZ, y = Y / ZZZ)
 template <class C>
 struct XyzzBatchAffineBody {
-  typedef Fd<typename C::FqP> Fq;
+  typedef typename CoordOf<C>::type Fq;
   typedef XyzzD<C> Pt;
-  static constexpr int FN = Fq::N, AW = 2 * FN;
+  static constexpr int FN = Fq::N, AW = AffD<C>::WORDS;
   const uint32_t* in;        // n x Pt::WORDS
   uint32_t* scratch;         // n x Fq
   uint32_t* out;             // n affine points

@@ -9,7 +9,16 @@ Per nv in {16, 20, 24} (or the sizes given): keys of 2^nv - 1 points (the length
   - the open of the smallest size in child processes with other values of PC_HIP_G2_SMALL_ROUND (read once per process).
 Keys are made of DISTINCT points without a device-side fixed-base multiplication: two pools of 2^12 Python-made points, point (a, b) of
 the key = P_a + Q_b by pc_hip_g2_srs_pair_sums (a periodic key would put equal points into one bucket and time the doubling branch).
-Timing needs a GPU: there is no fallback.  Prints one JSON line per measurement and a Markdown table."""
+Timing needs a GPU: there is no fallback.  Prints one JSON line per measurement and a Markdown table.
+
+`--setup [nv ..]` (default 16 20 22) times the parameters instead, on TRUE keys made by pc_hip_ml_setup from a random trapdoor:
+  - pc_hip_ml_setup as a whole and its host-bracketed phases (eq table, G1 level 0, G2 level 0, upper levels; timing on);
+  - G2 against G1 fixed-base multiplications per second at equal n = 2^nv (pc_hip_g2_fixed_base_batch_mul and
+    pc_hip_fixed_base_batch_mul on the same eq table, alternating);
+  - pc_hip_ml_trim, and pc_hip_ml_open on the trimmed key (a real key, not a periodic one);
+  - up to nv = 20, the only way to a resident pair-sum key without pc_hip_ml_setup: the levels on the host (read back from the
+    device key here; making them is not counted) uploaded and reduced by multilinear_pair_key -- the ratios to pc_hip_ml_trim alone
+    and to setup + trim, each with the run's minimum and maximum."""
 import json
 import os
 import statistics
@@ -91,9 +100,96 @@ def open_only(nv, pool_path, reps):
     ctx.close()
 
 
+def setup_leg(sizes):
+    ctx = pc.Context(0)
+    g = np.frombuffer(G.point_bytes(G.g1_generator(), True), dtype=np.uint8).copy()
+    h = np.frombuffer(G.point_bytes(G.generator()), dtype=np.uint8).copy()
+    rows = []
+    for nv in sizes:
+        n = 1 << nv
+        reps = 5
+        rng = np.random.default_rng(100 + nv)
+        t = random_fr(rng, nv)
+        ctx.set_timing(True)
+        totals, phases = [], []
+        keys = None
+        for it in range(reps + 1):                          # the first pass is the warm-up (workspace, staging)
+            if keys:
+                keys[0].free(); keys[1].free()
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            keys = ctx.ml_setup(CURVE, nv, g, h, t)[:2]
+            ms = (time.perf_counter() - t0) * 1e3
+            if it:
+                totals.append(ms); phases.append(ctx.last_msm_phases_ms()[:4])
+        ctx.set_timing(False)
+        gk, hk = keys
+        ph = [statistics.median(p[i] for p in phases) for i in range(4)]
+        # fixed-base rates at equal n, alternating, on the same scalars
+        eq = torch.empty((n, 4), dtype=torch.int64, device="cuda")
+        ctx.ml_eq_evals(CURVE, t, nv, eq.data_ptr())
+        o1 = torch.empty((n, 12), dtype=torch.int64, device="cuda")
+        o2 = torch.empty((n, 24), dtype=torch.int64, device="cuda")
+        f1 = lambda: ctx.fixed_base_batch_mul(CURVE, g.view(np.uint64), eq.data_ptr(), n, o1.data_ptr())
+        f2 = lambda: ctx.g2_fixed_base_batch_mul(CURVE, h, eq.data_ptr(), n, o2.data_ptr())
+        f1(); f2()
+        t1, t2 = [], []
+        for _ in range(reps):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); f2(); t2.append((time.perf_counter() - t0) * 1e3)
+            torch.cuda.synchronize(); t0 = time.perf_counter(); f1(); t1.append((time.perf_counter() - t0) * 1e3)
+        del eq, o1, o2
+        g1_ms, g2_ms = statistics.median(t1), statistics.median(t2)
+        # trim and open on the real key
+        made = []
+
+        def trim():
+            for k in made:
+                k.free()
+            made[:] = ctx.ml_trim(gk, hk, nv, nv)
+        trm = stats(trim, 1, reps)
+        ev = torch.from_numpy(random_fr(rng, n).view(np.int64)).cuda()
+        pt = random_fr(rng, nv)
+        opn = stats(lambda: made[1].ml_open(ev, nv, pt), 2, reps)
+        rec = dict(kind="setup", nv=nv, setup_ms=statistics.median(totals), setup_min_max_ms=(min(totals), max(totals)), eq_table_ms=ph[0], g1_level0_ms=ph[1],
+                   g2_level0_ms=ph[2], upper_levels_ms=ph[3], g1_fixed_base_ms=g1_ms, g1_min_max_ms=(min(t1), max(t1)), g2_fixed_base_ms=g2_ms,
+                   g2_min_max_ms=(min(t2), max(t2)), g1_mul_per_s=n / g1_ms * 1e3, g2_mul_per_s=n / g2_ms * 1e3, ratio_g2_over_g1=g2_ms / g1_ms,
+                   trim_ms=trm[0], trim_min_max_ms=trm[1:], open_real_key_ms=opn[0], open_min_max_ms=opn[1:])
+        if nv <= 20:
+            levels = [hk.read(pc.ml_level_offset(nv, i), n >> i) for i in range(nv)]
+            old = []
+
+            def upload():
+                for k in old:
+                    k.free()
+                old[:] = [pc.multilinear_pair_key(ctx, CURVE, levels)]
+            upl = stats(upload, 1, 3)
+            same = old[0].read(0, n - 1).tobytes() == made[1].read(0, n - 1).tobytes()
+            old[0].free()
+            del levels
+            rec.update(upload_pair_key_ms=upl[0], upload_min_max_ms=upl[1:], keys_equal=same, upload_over_trim=upl[0] / trm[0],
+                       upload_over_trim_min_max=(upl[1] / trm[2], upl[2] / trm[1]), upload_over_setup_plus_trim=upl[0] / (rec["setup_ms"] + trm[0]),
+                       upload_over_setup_plus_trim_min_max=(upl[1] / (max(totals) + trm[2]), upl[2] / (min(totals) + trm[1])))
+        rows.append(rec)
+        print(json.dumps(rec), flush=True)
+        for k in made + [gk, hk]:
+            k.free()
+        del ev
+        torch.cuda.empty_cache()
+        ctx.trim()
+    ctx.close()
+    print("\n| nv | setup ms (min-max) | eq table | G1 level 0 | G2 level 0 | upper levels | G1 mul/s | G2 mul/s | G2 / G1 | trim ms | open ms (real key) | upload + pair sums ms | / trim | / (setup + trim) |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        tail = (f"{r['upload_pair_key_ms']:.1f} | {r['upload_over_trim']:.0f} | {r['upload_over_setup_plus_trim']:.2f} ({r['upload_over_setup_plus_trim_min_max'][0]:.2f}-{r['upload_over_setup_plus_trim_min_max'][1]:.2f})"
+                if "upload_pair_key_ms" in r else "- | - | -")
+        print(f"| {r['nv']} | {r['setup_ms']:.2f} ({r['setup_min_max_ms'][0]:.2f}-{r['setup_min_max_ms'][1]:.2f}) | {r['eq_table_ms']:.2f} | {r['g1_level0_ms']:.2f} | {r['g2_level0_ms']:.2f} | "
+              f"{r['upper_levels_ms']:.2f} | {r['g1_mul_per_s']:.3g} | {r['g2_mul_per_s']:.3g} | {r['ratio_g2_over_g1']:.2f} | {r['trim_ms']:.2f} | {r['open_real_key_ms']:.2f} | {tail} |")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--open-only":
         return open_only(int(sys.argv[2]), sys.argv[3], int(sys.argv[4]))
+    if len(sys.argv) > 1 and sys.argv[1] == "--setup":
+        return setup_leg([int(x) for x in sys.argv[2:]] or [16, 20, 22])
     sizes = [int(x) for x in sys.argv[1:]] or [16, 20, 24]
     pool_path = os.path.join(tempfile.mkdtemp(prefix="g2_timing_"), "pools.npz")
     pa, pb = pools(pool_path)
