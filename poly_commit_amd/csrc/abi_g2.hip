@@ -1,16 +1,14 @@
 // C ABI of the gfx950 backend (include/pc_hip.h): G2 keys, the G2 MSM and MultilinearPC's setup, trim and open (multilinear_pc/mod.rs).
-// This unit also instantiates everything templated on G2 (g2.hpp, the fixed-base bodies of ipa.hpp, MsmPlan<G2Of<C>, HipBackend>):
-// BLS12-381 only.
+// This unit also instantiates everything templated on G2 (g2.hpp, fixed_base.hpp, MsmPlan<G2Of<C>, HipBackend>), BLS12-381 only,
+// and nothing of G1: the G1 half of the setup goes through pc::curve_ops.
 #include <chrono>
 #include "abi.hpp"
 #include "hip_backend_msm.hpp"
-#include "g2.hpp"
-#include "ipa.hpp"
+#include "fixed_base.hpp"
 
 namespace pc {
 namespace {
 
-typedef pc_curve_bls12_381 G1C;
 typedef G2Of<pc_curve_bls12_381> G2C;
 typedef pc_curve_bls12_381::FrP FrP;
 constexpr int G2_AW = AffD<G2C>::WORDS, G2_XW = XyzzD<G2C>::WORDS, FR_W = FrP::N;
@@ -77,70 +75,9 @@ void small_msm(HipBackend& be, const uint32_t* bases, const uint32_t* scalars_de
   host64::Xyzz64<G2C>::load(xyzz).store_affine(out_host);
 }
 
-// out[b] = in[2b] + in[2b + 1], b < count, for affine points of G on the device (PairSumsBody).  Slabs of 2^19 pairs: 252 MB of
-// workspace for G2 (an XYZZ sum and a prefix product per pair) whatever the key's size.  A lane adds and normalises K pairs around
-// ONE inversion, and the inversion is most of a lane's run time: K = 8 only where that still leaves 2^16 lanes (one wave on every
-// SIMD; these kernels hold one wave per SIMD for G2), fewer pairs per lane below -- with K = 8 and slabs of 2^17 throughout, every
-// launch was a quarter-filled machine waiting for 16384 serial chains (the upper levels of pc_hip_ml_setup took as long as the 2^nv
-// G2 multiplications of level 0).  `in` and `out` must not overlap.
-template <class G>
-void pair_sums_run(HipBackend& be, const uint32_t* in, size_t count, uint32_t* out) {
-  constexpr int AW = AffD<G>::WORDS, XW = XyzzD<G>::WORDS;
-  const size_t SLAB = (size_t)1 << 19;
-  for (size_t first = 0; first < count; first += SLAB) {
-    const size_t cnt = std::min(SLAB, count - first);
-    const uint32_t K = (uint32_t)std::min<size_t>(8, std::max<size_t>(1, cnt >> 16));
-    uint32_t* ws = (uint32_t*)be.workspace(cnt * (size_t)(XW + AW / 2) * 4);
-    PairSumsBody<G> b{in + 2 * first * (size_t)AW, ws, ws + cnt * (size_t)XW, out + first * (size_t)AW, (uint32_t)cnt, K};
-    be.launch(b, (cnt + K - 1) / K, 64);
-  }
-}
-
-// out[i] = scalars[i] * base, i < n: `base.batch_mul(scalars)` for one affine point of G (host) and n Montgomery scalars on the
-// device; affine results on the device.  What CurveOps::fixed_base does for G1 (curve_ops_impl.hpp), for either group and in slabs:
-// an XYZZ result over Fq2 is 384 bytes, so the results of one slab (2^18: 126 MB with the prefix products) are normalised before the
-// next slab's are made and the workspace does not grow with n.  Below FIXED_BASE_LADDER_BELOW scalars the table (4096 group
-// additions on the host) costs more than it saves: each lane runs its own double-and-add ladder.
-constexpr size_t FIXED_BASE_LADDER_BELOW = 4096, FIXED_BASE_SLAB = (size_t)1 << 18;
-template <class G>
-void fixed_base_run(HipBackend& be, const uint32_t* base, const uint32_t* scalars, size_t n, uint32_t* out) {
-  constexpr int AW = AffD<G>::WORDS, XW = XyzzD<G>::WORDS, FW = AW / 2;
-  if (!n) return;
-  if (n < FIXED_BASE_LADDER_BELOW) {
-    uint32_t* ws = (uint32_t*)be.workspace(((size_t)AW + n * (size_t)(XW + FW)) * 4);
-    uint32_t* dres = ws + AW;
-    be.copy_h2d(ws, base, (size_t)AW * 4);
-    ScalarMulStoreBody<G> body{{ws, scalars, 1u}, dres};
-    be.launch(body, n, 64);
-    XyzzBatchAffineBody<G> nb{dres, dres + n * (size_t)XW, out, (uint32_t)n, 1};
-    be.launch(nb, n, 64);
-    be.sync();
-    return;
-  }
-  // window table of the fixed base on the host: T[w][d-1] = d * 2^(8 w) * base, d = 1..128 (one inversion for all of it)
-  const uint32_t Wd = msm_num_windows(G::FrP::BITS, FIXED_BASE_C);
-  std::vector<uint32_t> tbl;
-  host64::fixed_base_window_table<G>(base, FIXED_BASE_C, Wd, tbl);
-  // device: table | XYZZ results of one slab | their prefix products
-  const size_t slab = std::min(n, FIXED_BASE_SLAB), tb = tbl.size() * 4;
-  uint8_t* ws = (uint8_t*)be.workspace(tb + slab * (size_t)(XW + FW) * 4);
-  uint32_t* dtbl = (uint32_t*)ws; uint32_t* dres = (uint32_t*)(ws + tb); uint32_t* dscr = dres + slab * (size_t)XW;
-  be.copy_h2d(dtbl, tbl.data(), tb);
-  const uint32_t K = 8;
-  for (size_t first = 0; first < n; first += slab) {
-    const size_t cnt = std::min(slab, n - first);
-    FixedBaseTableMulBody<G> body{scalars + first * (size_t)FR_W, dtbl, Wd, dres};
-    be.launch(body, cnt, 64);
-    XyzzBatchAffineBody<G> nb{dres, dscr, out + first * (size_t)AW, (uint32_t)cnt, K};
-    be.launch(nb, (cnt + K - 1) / K, 64);
-  }
-  be.sync();                                   // the host table goes out of scope
-}
-
 }  // namespace
 }  // namespace pc
 
-using pc::G1C;
 using pc::G2C;
 using pc::G2_AW;
 using pc::FR_W;
@@ -166,22 +103,7 @@ int pc_hip_g2_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t 
   int rc = guarded(ctx, [&]() {
     k = g2_key_create(ctx, curve, n);
     if (!k) return (int)PC_ERR_OOM;
-    if (n) {
-      if (where == PC_MEM_DEVICE) ctx->be.copy_d2d(k->bases, bases, n * pb);
-      else if (stride_bytes == pb) ctx->be.copy_h2d(k->bases, bases, n * pb);
-      else {
-        // Rust Affine{x, y, infinity}: repack, mapping the flag to the all-zero encoding
-        std::vector<uint8_t> packed(n * pb);
-        const uint8_t* src = (const uint8_t*)bases;
-        for (size_t i = 0; i < n; i++) {
-          const uint8_t* p = src + i * stride_bytes;
-          if (p[pb]) memset(&packed[i * pb], 0, pb); else memcpy(&packed[i * pb], p, pb);
-        }
-        ctx->be.copy_h2d(k->bases, packed.data(), n * pb);
-        ctx->be.sync();
-      }
-      ctx->be.sync();
-    }
+    key_base_fill(k, bases, n, stride_bytes, where);
     return (int)PC_OK;
   });
   if (rc != PC_OK) { if (k) g2_key_free(k); return rc; }
@@ -189,11 +111,7 @@ int pc_hip_g2_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t 
   return PC_OK;
 }
 
-void pc_hip_g2_srs_free(pc_g2_srs* k) {
-  if (!k) return;
-  if (k->ctx) { std::lock_guard<std::recursive_mutex> lk(k->ctx->mu); g2_key_free(k); }
-  else g2_key_free(k);
-}
+void pc_hip_g2_srs_free(pc_g2_srs* k) { key_free_locked(k, g2_key_free); }
 
 size_t pc_hip_g2_srs_len(const pc_g2_srs* k) { return k ? k->n : 0; }
 
@@ -205,14 +123,7 @@ int pc_hip_g2_srs_bytes_resident(const pc_g2_srs* k, size_t out[4]) {
   return PC_OK;
 }
 
-int pc_hip_g2_srs_read(pc_ctx* ctx, const pc_g2_srs* k, size_t offset, size_t count, void* out_host) {
-  if (!ctx || !k || k->ctx != ctx || offset > k->n || count > k->n - offset || (count && !out_host)) return PC_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    if (count) ctx->be.copy_d2h(out_host, k->bases + offset * (size_t)k->aw, count * (size_t)k->aw * 4);
-    return (int)PC_OK;
-  });
-}
+int pc_hip_g2_srs_read(pc_ctx* ctx, const pc_g2_srs* k, size_t offset, size_t count, void* out_host) { return key_base_read(ctx, k, offset, count, out_host); }
 
 int pc_hip_g2_srs_pair_sums(pc_ctx* ctx, const pc_g2_srs* in, size_t off, size_t count, pc_g2_srs* out, size_t out_off) {
   if (!ctx || !in || !out || in->ctx != ctx || out->ctx != ctx || in->curve != out->curve) return PC_ERR_INVALID_ARG;
@@ -247,7 +158,7 @@ int pc_hip_g2_fixed_base_batch_mul(pc_ctx* ctx, pc_curve curve, const void* h_ho
   if (n >= (1ull << 31)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
-    pc::fixed_base_run<G2C>(ctx->be, (const uint32_t*)h_host, (const uint32_t*)scalars_dev, n, (uint32_t*)out_points_dev);
+    pc::fixed_base_run<G2C>(ctx->be, (const uint32_t*)h_host, (const uint32_t*)scalars_dev, n, (uint32_t*)out_points_dev, pc::FIXED_BASE_K_ML);
     return (int)PC_OK;
   });
 }
@@ -264,7 +175,7 @@ int pc_hip_ml_setup(pc_ctx* ctx, pc_curve curve, unsigned nv, const void* g_xy_h
   *out_powers_of_g = nullptr; *out_powers_of_h = nullptr;
   pc_srs* G = nullptr; pc_g2_srs* H = nullptr;
   const size_t n0 = (size_t)1 << nv;
-  constexpr int G1_AW = pc::AffD<G1C>::WORDS;
+  const pc::CurveOps& g1 = pc::curve_ops(curve);
   int rc = guarded(ctx, [&]() {
     G = key_create(ctx, curve, 2 * n0 - 2);
     if (!G) return (int)PC_ERR_OOM;
@@ -289,14 +200,14 @@ int pc_hip_ml_setup(pc_ctx* ctx, pc_curve curve, unsigned nv, const void* g_xy_h
     pc::MlEqBody<pc::FrP> eb; eb.out = (uint32_t*)eq.dev; eb.set_point((const uint32_t*)t_host, nv);
     be.launch(eb, n0);
     bracket();
-    pc::fixed_base_run<G1C>(be, (const uint32_t*)g_xy_host, (const uint32_t*)eq.dev, n0, G->bases);
+    g1.fixed_base(be, (const uint32_t*)g_xy_host, (const uint32_t*)eq.dev, n0, G->bases, pc::FIXED_BASE_K_ML);
     bracket();
-    pc::fixed_base_run<G2C>(be, (const uint32_t*)h_host, (const uint32_t*)eq.dev, n0, H->bases);
+    pc::fixed_base_run<G2C>(be, (const uint32_t*)h_host, (const uint32_t*)eq.dev, n0, H->bases, pc::FIXED_BASE_K_ML);
     bracket();
     // L_i[2b] + L_i[2b + 1] = L_{i+1}[b]: every higher level is the pair sums of the one below; the sum of the last one is 1
     for (unsigned i = 0; i + 1 < nv; i++) {
       const size_t off = ml_level_off(nv, i), m = n0 >> i;
-      pc::pair_sums_run<G1C>(be, G->bases + off * G1_AW, m / 2, G->bases + (off + m) * G1_AW);
+      g1.pair_sums(be, G->bases + off * g1.aw, m / 2, G->bases + (off + m) * g1.aw);
       pc::pair_sums_run<G2C>(be, H->bases + off * G2_AW, m / 2, H->bases + (off + m) * G2_AW);
     }
     be.copy_h2d(H->bases + (2 * n0 - 2) * G2_AW, h_host, (size_t)G2_AW * 4);
@@ -304,7 +215,7 @@ int pc_hip_ml_setup(pc_ctx* ctx, pc_curve curve, unsigned nv, const void* g_xy_h
     bracket();
     if (g_mask_out_host)      // g_mask[i] = t_i * g (mod.rs:75): nv multiplications, on the host
       for (unsigned i = 0; i < nv; i++)
-        pc::curve_ops(curve).point_mul((const uint32_t*)g_xy_host, (const uint32_t*)t_host + (size_t)i * FR_W, (uint32_t*)g_mask_out_host + (size_t)i * G1_AW);
+        g1.point_mul((const uint32_t*)g_xy_host, (const uint32_t*)t_host + (size_t)i * FR_W, (uint32_t*)g_mask_out_host + (size_t)i * g1.aw);
     return (int)PC_OK;
   });
   if (rc != PC_OK) { if (G) key_free(G); if (H) g2_key_free(H); return rc; }
@@ -359,26 +270,14 @@ int pc_hip_g2_msm(pc_ctx* ctx, const pc_g2_srs* kc, size_t base_offset, const vo
 int pc_hip_g2_points_sum(pc_curve curve, const void* points, size_t count, void* out_xy) {
   if (!out_xy || (count && !points)) return PC_ERR_INVALID_ARG;
   if (int rc = g2_curve_check(curve)) return rc;
-  pc::XyzzD<G2C> acc = pc::XyzzD<G2C>::infinity();
-  for (size_t i = 0; i < count; i++) acc.add_affine(pc::AffD<G2C>::load((const uint32_t*)points + i * G2_AW));
-  acc.to_affine().store((uint32_t*)out_xy);
+  pc::host64::points_sum<G2C>((const uint32_t*)points, count, (uint32_t*)out_xy);
   return PC_OK;
 }
 
 int pc_hip_g2_point_mul(pc_curve curve, const void* point, const void* scalar_mont, void* out_xy) {
   if (!point || !scalar_mont || !out_xy) return PC_ERR_INVALID_ARG;
   if (int rc = g2_curve_check(curve)) return rc;
-  typedef pc::host64::Xyzz64<G2C> P64;
-  const uint32_t* pt = (const uint32_t*)point;
-  const pc::Fd<pc::FrP> kk = pc::Fd<pc::FrP>::load((const uint32_t*)scalar_mont).from_mont();
-  P64 base = P64::infinity();
-  if (!affine_is_zero(pt, G2_AW)) { base.X = P64::Fq::load(pt); base.Y = P64::Fq::load(pt + G2_AW / 2); base.ZZ = P64::Fq::one(); base.ZZZ = P64::Fq::one(); }
-  P64 acc = P64::infinity();
-  for (int bit = FR_W * 32 - 1; bit >= 0; bit--) {
-    acc = acc.dbl();
-    if ((kk.l[bit >> 5] >> (bit & 31)) & 1) acc.add(base);
-  }
-  acc.store_affine((uint32_t*)out_xy);
+  pc::host64::scalar_mul<G2C>((const uint32_t*)point, pc::Fd<pc::FrP>::load((const uint32_t*)scalar_mont).from_mont().l, (uint32_t*)out_xy);
   return PC_OK;
 }
 

@@ -68,7 +68,7 @@ int pc_hip_ec_fold(pc_ctx* ctx, pc_srs* srs, size_t n_half, const void* u_host) 
     drop_table(srs);                            // the key changes: its window tables are stale
     drop_many(srs);
     drop_fold_table(srs);
-    pc::curve_ops(srs->curve).ec_fold(ctx->be, srs->bases, n_half, (const uint32_t*)u_host);
+    pc::curve_ops(srs->curve).ec_fold_to(ctx->be, srs->bases, srs->bases, n_half, (const uint32_t*)u_host, nullptr, 0);
     return (int)PC_OK;
   });
 }
@@ -272,7 +272,7 @@ int pc_hip_fixed_base_batch_mul(pc_ctx* ctx, pc_curve curve, const void* g_xy_ho
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
     if (!n) return (int)PC_OK;
-    pc::curve_ops(curve).fixed_base(ctx->be, (const uint32_t*)g_xy_host, (const uint32_t*)scalars_dev, n, (uint32_t*)out_points_dev);
+    pc::curve_ops(curve).fixed_base(ctx->be, (const uint32_t*)g_xy_host, (const uint32_t*)scalars_dev, n, (uint32_t*)out_points_dev, pc::FIXED_BASE_K_KZG);
     return (int)PC_OK;
   });
 }

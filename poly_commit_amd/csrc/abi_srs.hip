@@ -18,24 +18,7 @@ int pc_hip_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t n, 
   int rc = guarded(ctx, [&]() {
     srs = key_create(ctx, curve, n);
     if (!srs) return (int)PC_ERR_OOM;
-    if (n) {
-      if (where == PC_MEM_DEVICE) {
-        ctx->be.copy_d2d(srs->bases, bases, n * pb);
-      } else if (stride_bytes == pb) {
-        ctx->be.copy_h2d(srs->bases, bases, n * pb);
-      } else {
-        // Rust Affine{x, y, infinity}: repack, mapping the flag to the (0,0) encoding
-        std::vector<uint8_t> packed(n * pb);
-        const uint8_t* src = (const uint8_t*)bases;
-        for (size_t i = 0; i < n; i++) {
-          const uint8_t* p = src + i * stride_bytes;
-          if (p[pb]) memset(&packed[i * pb], 0, pb); else memcpy(&packed[i * pb], p, pb);
-        }
-        ctx->be.copy_h2d(srs->bases, packed.data(), n * pb);
-        ctx->be.sync();
-      }
-      ctx->be.sync();
-    }
+    key_base_fill(srs, bases, n, stride_bytes, where);
     if (const char* e = getenv("PC_HIP_SEG_TAIL")) srs->cfg.seg_tail_lanes = (uint32_t)atoi(e);   // tuning experiments
     if (const char* e = getenv("PC_HIP_T2")) srs->cfg.T2 = (uint32_t)atoi(e);
     if (const char* e = getenv("PC_HIP_T2B")) srs->cfg.T2b = (uint32_t)atoi(e);
@@ -139,11 +122,7 @@ int pc_hip_universal_params_layout(pc_curve curve, const void* bytes, size_t n_b
 // threads (Drop of the last Arc<ResidentKey>, device::release, the LRU eviction of the Rust shim) while other threads may be inside
 // pc_hip_srs_upload / pc_hip_ctx_trim / any alloc: the context lock is held for the whole call (recursive: pc_hip_ctx_trim and the
 // work-cache recursion below re-enter).  The mutex lives in the context; pc_hip_shutdown releases every key still alive and leaves it with ctx == nullptr, so a key freed after its context never touches that mutex.
-void pc_hip_srs_free(pc_srs* srs) {
-  if (!srs) return;
-  if (srs->ctx) { std::lock_guard<std::recursive_mutex> lk(srs->ctx->mu); key_free(srs); }
-  else key_free(srs);
-}
+void pc_hip_srs_free(pc_srs* srs) { key_free_locked(srs, key_free); }
 int pc_hip_srs_precompute_ex(pc_ctx* ctx, pc_srs* srs, unsigned window_bits, size_t min_pairs, unsigned flags) {
   if (!ctx || !srs || srs->ctx != ctx || window_bits == 1 || window_bits > 23 || (flags & ~(unsigned)(PC_HIP_TABLE_GLV | PC_HIP_TABLE_GLV_IF_TIGHT | PC_HIP_TABLE_GLV_IF_LARGE))) return PC_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -274,13 +253,6 @@ int pc_hip_srs_fold_table_info(const pc_srs* srs, unsigned* out_levels, unsigned
   return PC_OK;
 }
 
-int pc_hip_srs_read(pc_ctx* ctx, const pc_srs* srs, size_t offset, size_t count, void* out_xy) {
-  if (!ctx || !srs || srs->ctx != ctx || offset + count > srs->n || (count && !out_xy)) return PC_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    if (count) ctx->be.copy_d2h(out_xy, srs->bases + offset * (size_t)srs->aw, count * (size_t)srs->aw * 4);
-    return (int)PC_OK;
-  });
-}
+int pc_hip_srs_read(pc_ctx* ctx, const pc_srs* srs, size_t offset, size_t count, void* out_xy) { return key_base_read(ctx, srs, offset, count, out_xy); }
 
 }  // extern "C"

@@ -9,6 +9,7 @@
 #include "ipa.hpp"
 #include "glv.hpp"
 #include "fold_table.hpp"
+#include "fixed_base.hpp"
 #include "serialize.hpp"
 
 namespace pc {
@@ -151,29 +152,6 @@ void build_window_table(HipBackend& be, const uint32_t* bases, uint32_t n, uint3
   else build_window_table_batched<C>(be, bases, n, c, Wd, table, stride);
 }
 
-// key[i] = affine(key[i] + u * key[half + i]): GLV split of the shared challenge on the host, one ladder per lane
-template <class C>
-void ec_fold_run(HipBackend& be, uint32_t* key, size_t half, const uint32_t* u_mont) {
-  typedef typename GlvOf<C>::T G;
-  Fd<typename C::FrP> u = Fd<typename C::FrP>::load(u_mont).from_mont();
-  uint64_t k[4]; memcpy(k, u.l, 32);
-  GlvSplit sp = glv_decompose<G>(k);
-  EcFoldGlvBody<C> body; body.key = key; body.half = (uint32_t)half;
-  body.n1.from_scalar(sp.k1); body.n2.from_scalar(sp.k2); body.neg1 = sp.neg1; body.neg2 = sp.neg2;
-  for (int i = 0; i < C::FqP::N; i++) body.beta[i] = G::BETA_MONT[i];
-  constexpr int FN = C::FqP::N;
-  if (half >= 4096) {
-    // ladders leave Jacobian results; one inversion per K of them (normalize_batch, ipa_pc/mod.rs:706-708)
-    uint32_t* ws = (uint32_t*)be.workspace(half * (size_t)4 * FN * 4);
-    body.jac_out = ws;
-    be.launch(body, half, 64);
-    const uint32_t K = half >= ((size_t)1 << 20) ? 16 : half >= ((size_t)1 << 17) ? 8 : 4;     // >= 2^14 lanes while it matters
-    JacBatchAffineBody<C> nb{ws, ws + half * (size_t)3 * FN, key, (uint32_t)half, K};
-    be.launch(nb, (half + K - 1) / K, 64);
-  } else be.launch(body, half, 64);
-  be.sync();
-}
-
 // out[i] = affine(in[i] + u * in[half + i]), i < half (out may be `in` itself: the in-place fold).  table != null: the first
 // fold of an opening from the committer key's (one-level) fold table of width-w NAF digits, else the GLV ladder per element.
 template <class C>
@@ -185,6 +163,7 @@ void ec_fold_to_run(HipBackend& be, const uint32_t* in, uint32_t* out, size_t ha
     if (ec_fold_table_run<C>(be, in, out, half, half, 1, us, w, table)) return;
     // a split that does not fit the table's rows (never seen: |k1|, |k2| <= 2^128): the ladder below
   }
+  // GLV split of the shared challenge on the host, one ladder per lane
   Fd<typename C::FrP> u = Fd<typename C::FrP>::load(u_mont).from_mont();
   uint64_t k[4]; memcpy(k, u.l, 32);
   GlvSplit sp = glv_decompose<G>(k);
@@ -193,10 +172,11 @@ void ec_fold_to_run(HipBackend& be, const uint32_t* in, uint32_t* out, size_t ha
   body.n1 = n1; body.n2 = n2; body.neg1 = sp.neg1; body.neg2 = sp.neg2;
   for (int i = 0; i < FN; i++) body.beta[i] = G::BETA_MONT[i];
   if (half >= 4096) {
+    // ladders leave Jacobian results; one inversion per K of them (normalize_batch, ipa_pc/mod.rs:706-708)
     uint32_t* ws = (uint32_t*)be.workspace(half * (size_t)4 * FN * 4);
     body.jac_out = ws;
     be.launch(body, half, 64);
-    const uint32_t K = half >= ((size_t)1 << 20) ? 16 : half >= ((size_t)1 << 17) ? 8 : 4;
+    const uint32_t K = half >= ((size_t)1 << 20) ? 16 : half >= ((size_t)1 << 17) ? 8 : 4;     // >= 2^14 lanes while it matters
     JacBatchAffineBody<C> nb{ws, ws + half * (size_t)3 * FN, out, (uint32_t)half, K};
     be.launch(nb, (half + K - 1) / K, 64);
   } else be.launch(body, half, 64);
@@ -212,9 +192,6 @@ struct CurveOpsImpl {
   static void window_table(HipBackend& be, const uint32_t* bases, uint32_t n, uint32_t c, uint32_t Wd, uint32_t* table, uint32_t stride) {
     build_window_table<C>(be, bases, n, c, Wd, table, stride);
   }
-  static void ec_fold(HipBackend& be, uint32_t* key, size_t half, const uint32_t* u_mont) {
-    ec_fold_run<C>(be, key, half, u_mont);
-  }
   static void ec_fold_to(HipBackend& be, const uint32_t* in, uint32_t* out, size_t half, const uint32_t* u_mont, const uint32_t* table, uint32_t w) {
     ec_fold_to_run<C>(be, in, out, half, u_mont, table, w);
   }
@@ -229,44 +206,8 @@ struct CurveOpsImpl {
   static void fr_inv(const uint32_t* a, uint32_t* out) { Fd<typename C::FrP>::load(a).inv().store(out); }
   static void fr_one(uint32_t* out) { Fd<typename C::FrP>::one().store(out); }
   static void fold_table_build(HipBackend& be, const uint32_t* pts, size_t count, uint32_t w, uint32_t* table) { fold_table_build_run<C>(be, pts, count, w, table); }
-  static void fixed_base(HipBackend& be, const uint32_t* g, const uint32_t* scalars, size_t n, uint32_t* out) {
-    if (n < 4096) {          // a handful of scalars: the per-lane ladder, no table
-      FixedBaseMulBody<C> body; body.scalars = scalars; body.out = out;
-      for (int i = 0; i < AW; i++) body.g[i] = g[i];
-      be.launch(body, n, 64); be.sync();
-      return;
-    }
-    // window table of the fixed base on the host: T[w][d-1] = d * 2^(8 w) * g, d = 1..128 (one inversion for all of it)
-    typedef host64::Xyzz64<C> P64;
-    constexpr int FW = C::FqP::N, XW = XyzzD<C>::WORDS;
-    const uint32_t Wd = msm_num_windows(C::FrP::BITS, FIXED_BASE_C), half = 1u << (FIXED_BASE_C - 1);
-    std::vector<uint32_t> xyzz((size_t)Wd * half * XW), tbl((size_t)Wd * half * AW);
-    P64 base = P64::infinity();
-    bool inf = true; for (int i = 0; i < AW; i++) inf &= g[i] == 0;
-    if (!inf) { base.X = P64::Fq::load(g); base.Y = P64::Fq::load(g + FW); base.ZZ = P64::Fq::one(); base.ZZZ = P64::Fq::one(); }
-    for (uint32_t w = 0; w < Wd; w++) {
-      P64 cur = base;
-      for (uint32_t d = 0; d < half; d++) {
-        cur.X.store(&xyzz[((size_t)w * half + d) * XW]); cur.Y.store(&xyzz[((size_t)w * half + d) * XW + FW]);
-        cur.ZZ.store(&xyzz[((size_t)w * half + d) * XW + 2 * FW]); cur.ZZZ.store(&xyzz[((size_t)w * half + d) * XW + 3 * FW]);
-        cur.add(base);
-      }
-      for (uint32_t k = 0; k < FIXED_BASE_C; k++) base = base.dbl();
-    }
-    host64::batch_to_affine<C>(xyzz.data(), (size_t)Wd * half, tbl.data());
-    // device: table | XYZZ results | prefix products
-    const size_t tb = tbl.size() * 4, rb = n * (size_t)XW * 4, sb = n * (size_t)FW * 4;
-    uint8_t* ws = (uint8_t*)be.workspace(tb + rb + sb);
-    uint32_t* dtbl = (uint32_t*)ws; uint32_t* dres = (uint32_t*)(ws + tb); uint32_t* dscr = (uint32_t*)(ws + tb + rb);
-    be.copy_h2d(dtbl, tbl.data(), tb);
-    be.sync();                                   // the host vectors go out of scope below
-    FixedBaseTableMulBody<C> body{scalars, dtbl, Wd, dres};
-    be.launch(body, n, 64);
-    const uint32_t K = 16;
-    XyzzBatchAffineBody<C> nb{dres, dscr, out, (uint32_t)n, K};
-    be.launch(nb, (n + K - 1) / K, 64);
-    be.sync();
-  }
+  static void fixed_base(HipBackend& be, const uint32_t* g, const uint32_t* scalars, size_t n, uint32_t* out, uint32_t K) { fixed_base_run<C>(be, g, scalars, n, out, K); }
+  static void pair_sums(HipBackend& be, const uint32_t* in, size_t count, uint32_t* out) { pair_sums_run<C>(be, in, count, out); }
   static uint32_t srs_decode(HipBackend& be, const uint8_t* bytes_dev, size_t n, int compressed, uint32_t* out) {
     uint32_t* bad = (uint32_t*)be.workspace(4);
     be.memset(bad, 0, 4);
@@ -279,27 +220,12 @@ struct CurveOpsImpl {
     SrsEncodeBody<C> b{pts_dev, (uint32_t)n, compressed ? 1u : 0u, C::FqP::BITS == 381 ? 1u : 0u, out_dev};
     be.launch(b, n, 64);
   }
-  static void points_sum(const uint32_t* pts, size_t count, uint32_t* out) {
-    XyzzD<C> acc = XyzzD<C>::infinity();
-    for (size_t i = 0; i < count; i++) acc.add_affine(AffD<C>::load(pts + i * AW));
-    acc.to_affine().store(out);
-  }
+  static void points_sum(const uint32_t* pts, size_t count, uint32_t* out) { host64::points_sum<C>(pts, count, out); }
   static void point_mul(const uint32_t* pt, const uint32_t* k_mont, uint32_t* out) {
-    typedef host64::Xyzz64<C> P64;
-    constexpr int FW = C::FqP::N;
-    Fd<typename C::FrP> k = Fd<typename C::FrP>::load(k_mont).from_mont();
-    bool inf = true; for (int i = 0; i < 2 * FW; i++) inf &= pt[i] == 0;
-    P64 base = P64::infinity();
-    if (!inf) { base.X = P64::Fq::load(pt); base.Y = P64::Fq::load(pt + FW); base.ZZ = P64::Fq::one(); base.ZZZ = P64::Fq::one(); }
-    P64 acc = P64::infinity();
-    for (int bit = C::FrP::N * 32 - 1; bit >= 0; bit--) {
-      acc = acc.dbl();
-      if ((k.l[bit >> 5] >> (bit & 31)) & 1) acc.add(base);
-    }
-    acc.store_affine(out);
+    host64::scalar_mul<C>(pt, Fd<typename C::FrP>::load(k_mont).from_mont().l, out);
   }
   static CurveOps table() {
-    return CurveOps{AW, (uint32_t)C::FrP::BITS, &make_runner, &window_table, &ec_fold, &ec_fold_to, &ec_fold_table, &fold_table_build, (uint32_t)FOLD_ROWS, &fixed_base, &srs_decode, &srs_encode, &points_sum, &point_mul, &fr_mul, &fr_inv, &fr_one};
+    return CurveOps{AW, (uint32_t)C::FrP::BITS, &make_runner, &window_table, &ec_fold_to, &ec_fold_table, &fold_table_build, (uint32_t)FOLD_ROWS, &fixed_base, &pair_sums, &srs_decode, &srs_encode, &points_sum, &point_mul, &fr_mul, &fr_inv, &fr_one};
   }
 };
 

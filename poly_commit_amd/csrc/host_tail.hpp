@@ -108,6 +108,8 @@ struct F64x2 {
 
 }  // namespace host64
 template <class C1> struct G2Of;      // ec.hpp
+template <class C> struct AffD;
+template <class C> struct XyzzD;
 namespace host64 {
 template <class C> struct Coord64Of { typedef F64<typename C::FqP> type; };
 template <class C1> struct Coord64Of<G2Of<C1>> { typedef F64x2<typename C1::FqP> type; };
@@ -121,6 +123,13 @@ struct Xyzz64 {
   bool is_inf() const { return ZZ.is_zero(); }
   void store(uint32_t* p) const { X.store(p); Y.store(p + FW); ZZ.store(p + 2 * FW); ZZZ.store(p + 3 * FW); }
   static Xyzz64 load(const uint32_t* p) { Xyzz64 r; r.X = Fq::load(p); r.Y = Fq::load(p + FW); r.ZZ = Fq::load(p + 2 * FW); r.ZZZ = Fq::load(p + 3 * FW); return r; }
+  // an affine point x||y (2 * FW words; all zero: infinity)
+  static Xyzz64 from_affine(const uint32_t* xy) {
+    bool inf = true; for (int i = 0; i < 2 * FW; i++) inf &= xy[i] == 0;
+    if (inf) return infinity();
+    Xyzz64 r; r.X = Fq::load(xy); r.Y = Fq::load(xy + FW); r.ZZ = r.ZZZ = Fq::one();
+    return r;
+  }
   Xyzz64 dbl() const {   // dbl-2008-s-1, a = 0
     if (is_inf() || Y.is_zero()) return infinity();
     Xyzz64 r;
@@ -149,6 +158,26 @@ struct Xyzz64 {
     X.mul(t.mul(ZZZ)).store(out); Y.mul(t.mul(ZZ)).store(out + FW);
   }
 };
+
+// out = k * pt for an affine point pt, as an affine point: double-and-add from the top bit of the canonical scalar (G::FrP::N words)
+template <class G>
+void scalar_mul(const uint32_t* pt, const uint32_t* k_canonical, uint32_t* out_affine) {
+  const Xyzz64<G> base = Xyzz64<G>::from_affine(pt);
+  Xyzz64<G> acc = Xyzz64<G>::infinity();
+  for (int bit = G::FrP::N * 32 - 1; bit >= 0; bit--) {
+    acc = acc.dbl();
+    if ((k_canonical[bit >> 5] >> (bit & 31)) & 1) acc.add(base);
+  }
+  acc.store_affine(out_affine);
+}
+
+// out = the sum of `count` affine points of G as an affine point (the group law of the device code, ec.hpp, run on the host)
+template <class G>
+void points_sum(const uint32_t* pts, size_t count, uint32_t* out_affine) {
+  XyzzD<G> acc = XyzzD<G>::infinity();
+  for (size_t i = 0; i < count; i++) acc.add_affine(AffD<G>::load(pts + i * AffD<G>::WORDS));
+  acc.to_affine().store(out_affine);
+}
 
 struct WeightedPoint { uint32_t exponent; const uint32_t* xyzz; };
 
@@ -200,9 +229,7 @@ void fixed_base_window_table(const uint32_t* base, uint32_t c, uint32_t Wd, std:
   const uint32_t half = 1u << (c - 1);
   std::vector<uint32_t> xyzz((size_t)Wd * half * 4 * FW);
   tbl.assign((size_t)Wd * half * 2 * FW, 0);
-  P b = P::infinity();
-  bool inf = true; for (int i = 0; i < 2 * FW; i++) inf &= base[i] == 0;
-  if (!inf) { b.X = P::Fq::load(base); b.Y = P::Fq::load(base + FW); b.ZZ = P::Fq::one(); b.ZZZ = P::Fq::one(); }
+  P b = P::from_affine(base);
   for (uint32_t w = 0; w < Wd; w++) {
     P cur = b;
     for (uint32_t d = 0; d < half; d++) { cur.store(&xyzz[((size_t)w * half + d) * 4 * FW]); cur.add(b); }

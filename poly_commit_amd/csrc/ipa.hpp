@@ -183,10 +183,10 @@ struct EcFoldBody {
   }
 };
 
-// out[i] = scalars[i] * g for one fixed base g: `g.batch_mul(powers_of_beta)`, the SRS generation
-// of KZG10::setup (poly-commit/src/kzg10/mod.rs:76,83).  One lane per scalar (per-lane NAF);
-// affine output.  Used to build TRUE structured reference strings for the trapdoor-checked
-// end-to-end tests, not on the commit/open path.
+// out[i] = scalars[i] * g by the NAF ladder above, one lane per scalar with its own recoding.  Host-stepped only: the library
+// launches no kernel of it (fixed_base.hpp multiplies by a fixed base).  tests/emu steps it to check NafMasks::from_scalar -- the
+// recoding the key fold's EcFoldGlvBody takes its two half-scalars in -- and naf_mul / JacD on scalars whose NAF carries out of the
+// top limb, which no fold challenge reaches deterministically.
 template <class C>
 struct FixedBaseMulBody {
   static constexpr int AW = 2 * Fd<typename C::FqP>::N;
@@ -201,8 +201,10 @@ struct FixedBaseMulBody {
   }
 };
 
-// The same batch_mul with a window table of the fixed base, what ark-ec's ScalarMul::batch_mul does
-// (`g.batch_mul(&powers_of_beta)`, poly-commit/src/kzg10/mod.rs:76,83): T[w][d-1] = d * 2^(8 w) * g for d = 1..128 and
+// out[i] = scalars[i] * g for one fixed base g: `g.batch_mul(powers_of_beta)`, the SRS generation of KZG10::setup
+// (poly-commit/src/kzg10/mod.rs:76,83).  Used to build TRUE structured reference strings for the trapdoor-checked end-to-end
+// tests and MultilinearPC's parameters, not on the commit/open path.  With a window table of the fixed
+// base, as ark-ec's ScalarMul::batch_mul does: T[w][d-1] = d * 2^(8 w) * g for d = 1..128 and
 // the 32 (31 for 254 bits) byte windows of a scalar; a multiplication is then at most one mixed addition per window of the
 // signed radix-256 recoding -- no doublings: ~320 field products instead of ~2900 for the per-lane NAF ladder.  The table
 // (4096 affine points, 393 KB for BLS12-381) is built on the host per call and read through L2.  Results stay in XYZZ

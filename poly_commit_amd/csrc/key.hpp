@@ -2,6 +2,9 @@
 // and the derived keys an opening hangs on it (the working key it folds into, the fixed key of the late rounds).  Host code only, no
 // kernels.  The units of the C ABI (abi_*.hip) go through the functions below: none of them touches parent, work_cache,
 // fixed_cache, work_out or pc_ctx::keys, and none creates or deletes a pc_srs or an MsmLane.
+// pc_srs (G1) and pc_g2_srs (G2) are two types over one base, pc_key_base: what only needs the base -- filling a key from the
+// caller's points, reading it back, the registry of its context, the free under the context's lock -- is written once, over the
+// base and the point size.
 #pragma once
 #include <algorithm>
 #include <map>
@@ -11,6 +14,7 @@
 #include <string>
 #include <vector>
 #include <stdlib.h>
+#include <string.h>
 #include "pc_internal.hpp"
 
 // One independent MSM pipeline: own stream, own workspace.  Several lanes per SRS let the
@@ -46,14 +50,19 @@ struct pc_ctx {
   float brakedown_phases[4] = {0, 0, 0, 0};
 };
 
+// What a key of either group is: n affine points resident on the device, registered in its context
+struct pc_key_base {
+  pc_ctx* ctx = nullptr;         // null: the context was shut down under the key (a tombstone: nothing left to release)
+  pc_curve curve = PC_CURVE_BLS12_381;
+  size_t n = 0;
+  uint32_t* bases = nullptr;     // packed coordinates: x||y (G1), x.c0 || x.c1 || y.c0 || y.c1 (G2); all zero = infinity
+  int aw = 0;                    // words per affine point
+};
+
 // Independent pipelines per SRS (stream + workspace each), used round-robin; a pipeline that still
 // holds a job is drained before it is reused.
 static constexpr int PC_MSM_LANES = 3;
-struct pc_srs {
-  pc_ctx* ctx = nullptr;
-  pc_curve curve = PC_CURVE_BLS12_381;
-  size_t n = 0;
-  uint32_t* bases = nullptr;     // packed x||y
+struct pc_srs : pc_key_base {
   uint32_t* table = nullptr;     // precomputed window table (pc_hip_srs_precompute), or null
   uint32_t* fold_tbl = nullptr;  // fold table (pc_hip_srs_precompute_fold[_ex]) of the key points [fold_half, fold_half + fold_pts), or null
   size_t fold_half = 0;          // points of the key the table leaves out = size of the key it folds to: n / 2 (one level) or n / 4 (two)
@@ -65,7 +74,6 @@ struct pc_srs {
   pc_srs* work_cache = nullptr;  // a returned working key, ready for reuse
   pc_srs* fixed_cache = nullptr; // pc_hip_ipa_open_rounds: the key object of the late rounds' FIXED key (n0 points, its window table, its pipelines), refilled by every opening
   pc_srs* work_out = nullptr;    // the working key currently handed out
-  int aw = 0;                    // words per affine point
   pc::MsmConfig cfg;
   MsmLane* lanes[PC_MSM_LANES] = {nullptr, nullptr, nullptr};
   int next_lane = 0;
@@ -104,6 +112,71 @@ static int guarded(pc_ctx* ctx, Fn fn) {
   } catch (const std::exception& e) {
     ctx->last_error = e.what(); return PC_ERR_HIP;
   }
+}
+
+// ---- what the keys of both groups share (K: pc_srs or pc_g2_srs) -----------------------------
+
+// A key object of n points of point_bytes each with its bases buffer, registered in `registry`.  Call inside guarded(): a failed
+// device allocation throws, with the object already released by free_key.  Null: no host memory.
+template <class K, class Free>
+inline K* key_base_create(std::vector<K*>& registry, pc_ctx* ctx, pc_curve curve, size_t n, size_t point_bytes, Free free_key) {
+  K* k = new (std::nothrow) K();
+  if (!k) return nullptr;
+  k->ctx = ctx; k->curve = curve; k->n = n; k->aw = (int)(point_bytes / 4);
+  registry.push_back(k);
+  try { k->bases = (uint32_t*)ctx->be.alloc((n ? n : 1) * point_bytes); }
+  catch (...) { free_key(k); throw; }
+  return k;
+}
+// out of the registry, bases buffer freed (the context is alive)
+template <class K>
+inline void key_base_release(std::vector<K*>& registry, K* k) {
+  registry.erase(std::remove(registry.begin(), registry.end(), k), registry.end());
+  if (k->bases) k->ctx->be.free(k->bases);
+  k->bases = nullptr; k->n = 0;
+}
+// pc_hip_shutdown: every key still alive gives up what it holds on the device and stays behind as a tombstone
+template <class K, class Release>
+inline void key_registry_shutdown(std::vector<K*>& registry, Release release_device) {
+  const std::vector<K*> alive = registry;
+  for (K* k : alive) { release_device(k); k->ctx = nullptr; }
+  registry.clear();
+}
+// pc_hip_[g2_]srs_free: under the context's lock, or -- the context is gone, and its mutex with it -- just the tombstone
+template <class K, class Free>
+inline void key_free_locked(K* k, Free free_key) {
+  if (!k) return;
+  if (k->ctx) { std::lock_guard<std::recursive_mutex> lk(k->ctx->mu); free_key(k); }
+  else free_key(k);
+}
+// Fill the key from the caller's n points (inside guarded()): device memory or packed host memory as they are; a host array of
+// Rust Affine{x, y, infinity} (stride > point bytes) is repacked, the flag byte behind the coordinates mapped to the all-zero encoding
+inline void key_base_fill(pc_key_base* k, const void* points, size_t n, size_t stride_bytes, pc_mem where) {
+  if (!n) return;
+  pc::HipBackend& be = k->ctx->be;
+  const size_t pb = (size_t)k->aw * 4;
+  if (where == PC_MEM_DEVICE) be.copy_d2d(k->bases, points, n * pb);
+  else if (stride_bytes == pb) be.copy_h2d(k->bases, points, n * pb);
+  else {
+    std::vector<uint8_t> packed(n * pb);
+    const uint8_t* src = (const uint8_t*)points;
+    for (size_t i = 0; i < n; i++) {
+      const uint8_t* p = src + i * stride_bytes;
+      if (p[pb]) memset(&packed[i * pb], 0, pb); else memcpy(&packed[i * pb], p, pb);
+    }
+    be.copy_h2d(k->bases, packed.data(), n * pb);
+    be.sync();                                 // `packed` goes out of scope
+  }
+  be.sync();
+}
+// points [offset, offset + count) of the key to the host: a whole entry point (pc_hip_srs_read, pc_hip_g2_srs_read)
+inline int key_base_read(pc_ctx* ctx, const pc_key_base* k, size_t offset, size_t count, void* out_host) {
+  if (!ctx || !k || k->ctx != ctx || offset > k->n || count > k->n - offset || (count && !out_host)) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    if (count) ctx->be.copy_d2h(out_host, k->bases + offset * (size_t)k->aw, count * (size_t)k->aw * 4);
+    return (int)PC_OK;
+  });
 }
 
 // ---- lanes and jobs --------------------------------------------------------------------------
@@ -246,13 +319,12 @@ inline void key_release_device(pc_srs* srs) {
       srs->lanes[i]->inflight->done = true; srs->lanes[i]->inflight->status = PC_ERR_INVALID_ARG;
     }
   key_delete_lanes(srs);
-  { auto& ks = srs->ctx->keys; ks.erase(std::remove(ks.begin(), ks.end(), srs), ks.end()); }
-  if (srs->bases) srs->ctx->be.free(srs->bases);
   drop_fold_table(srs);
   drop_batch_many(srs);
   if (srs->table) srs->ctx->be.free(srs->table);
   drop_many(srs);
-  srs->bases = srs->table = nullptr; srs->n = 0;
+  srs->table = nullptr;
+  key_base_release(srs->ctx->keys, srs);      // last: it zeroes n and bases
 }
 
 // the derived keys that `owners` cache (every work_cache, then every fixed_cache), detached from them
@@ -288,13 +360,8 @@ inline void key_free_derived(pc_srs* srs) {
 // A key object of n points of `curve` with its bases buffer, registered in its context, cfg = the context's.  Call inside guarded():
 // a failed device allocation throws, with the object already released.  Null: no host memory.
 inline pc_srs* key_create(pc_ctx* ctx, pc_curve curve, size_t n) {
-  pc_srs* srs = new (std::nothrow) pc_srs();
-  if (!srs) return nullptr;
-  const size_t pb = 2 * (size_t)fq_bytes(curve);
-  srs->ctx = ctx; srs->curve = curve; srs->n = n; srs->aw = (int)(pb / 4); srs->cfg = ctx->msm_cfg;
-  ctx->keys.push_back(srs);
-  try { srs->bases = (uint32_t*)ctx->be.alloc((n ? n : 1) * pb); }
-  catch (...) { key_free(srs); throw; }
+  pc_srs* srs = key_base_create(ctx->keys, ctx, curve, n, 2 * (size_t)fq_bytes(curve), key_free);
+  if (srs) srs->cfg = ctx->msm_cfg;
   return srs;
 }
 
@@ -367,11 +434,10 @@ inline void keys_shutdown(pc_ctx* ctx) {
   // Keys that outlive their context (Drop order of an Arc<ResidentKey> against the context, a Python object collected late): their
   // device memory and pipelines go now, the host object stays behind as a tombstone (ctx = nullptr) that a later pc_hip_srs_free
   // only deletes -- it must never lock a mutex inside the context deleted below.  Cached working keys are held by nobody: deleted.
-  std::vector<pc_srs*> alive = ctx->keys, cached = detach_cached(alive);
-  for (pc_srs* s : alive) { s->parent = nullptr; s->work_out = nullptr; }
-  for (pc_srs* s : alive) { key_release_device(s); s->ctx = nullptr; }
+  const std::vector<pc_srs*> cached = detach_cached(ctx->keys);
+  for (pc_srs* s : ctx->keys) { s->parent = nullptr; s->work_out = nullptr; }
+  key_registry_shutdown(ctx->keys, key_release_device);
   for (pc_srs* s : cached) delete s;
-  ctx->keys.clear();
 }
 
 // pc_hip_ctx_trim's share of the keys
@@ -423,12 +489,7 @@ struct G2Lane {
   pc::G2Runner* runner = nullptr;
   ~G2Lane() { delete runner; be.destroy(); }
 };
-struct pc_g2_srs {
-  pc_ctx* ctx = nullptr;
-  pc_curve curve = PC_CURVE_BLS12_381;
-  size_t n = 0;
-  uint32_t* bases = nullptr;     // packed x.c0 || x.c1 || y.c0 || y.c1
-  int aw = 0;                    // words per affine point
+struct pc_g2_srs : pc_key_base {
   G2Lane* lane = nullptr;
 };
 inline int g2_point_bytes(pc_curve c) { return 4 * fq_bytes(c); }
@@ -437,21 +498,12 @@ inline void g2_key_release_device(pc_g2_srs* k) {
   if (!k->ctx) return;
   (void)hipSetDevice(k->ctx->device);
   delete k->lane; k->lane = nullptr;
-  { auto& ks = k->ctx->g2_keys; ks.erase(std::remove(ks.begin(), ks.end(), k), ks.end()); }
-  if (k->bases) k->ctx->be.free(k->bases);
-  k->bases = nullptr; k->n = 0;
+  key_base_release(k->ctx->g2_keys, k);
 }
 inline void g2_key_free(pc_g2_srs* k) { g2_key_release_device(k); delete k; }
 // call inside guarded(): a failed device allocation throws, with the object already released.  Null: no host memory.
 inline pc_g2_srs* g2_key_create(pc_ctx* ctx, pc_curve curve, size_t n) {
-  pc_g2_srs* k = new (std::nothrow) pc_g2_srs();
-  if (!k) return nullptr;
-  const size_t pb = (size_t)g2_point_bytes(curve);
-  k->ctx = ctx; k->curve = curve; k->n = n; k->aw = (int)(pb / 4);
-  ctx->g2_keys.push_back(k);
-  try { k->bases = (uint32_t*)ctx->be.alloc((n ? n : 1) * pb); }
-  catch (...) { g2_key_free(k); throw; }
-  return k;
+  return key_base_create(ctx->g2_keys, ctx, curve, n, (size_t)g2_point_bytes(curve), g2_key_free);
 }
 // {bases, 0, 0, pipeline} bytes of one G2 key (the layout of key_bytes: G2 has no tables)
 inline void g2_key_bytes(const pc_g2_srs* k, size_t out[4]) {
@@ -459,11 +511,7 @@ inline void g2_key_bytes(const pc_g2_srs* k, size_t out[4]) {
   out[3] = k->lane ? k->lane->be.bytes_live : 0;
 }
 // pc_hip_shutdown's share
-inline void g2_keys_shutdown(pc_ctx* ctx) {
-  std::vector<pc_g2_srs*> alive = ctx->g2_keys;
-  for (pc_g2_srs* k : alive) { g2_key_release_device(k); k->ctx = nullptr; }
-  ctx->g2_keys.clear();
-}
+inline void g2_keys_shutdown(pc_ctx* ctx) { key_registry_shutdown(ctx->g2_keys, g2_key_release_device); }
 // pc_hip_ctx_trim's share: an idle pipeline gives its sort / scan scratch back
 inline void g2_keys_trim(pc_ctx* ctx) {
   for (pc_g2_srs* k : ctx->g2_keys) if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }

@@ -4,9 +4,15 @@
 //   abi_<subject>.hip  the extern "C" entry points (include/pc_hip.h), one unit per subject: ctx (context, errors, memory, timing),
 //                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa, lincode (the Brakedown code object); staging,
 //                      error translation
-//   key.hpp            host only: the key object (pc_srs), its pipelines and the derived keys of an opening -- their whole lifetime
+//   key.hpp            host only: the key objects -- pc_key_base and what G1 and G2 keys share over it (fill, read-back, registry,
+//                      locked free), pc_srs with its pipelines and the derived keys of an opening, pc_g2_srs -- their whole lifetime
 //   abi.hpp            host only: the staging helpers more than one abi unit uses
-//   curve_<name>.hip   everything templated on one curve: MSM pipeline, window table, key fold, fixed-base mul
+//   curve_<name>.hip   everything templated on one curve: MSM pipeline, window table, key fold, fixed-base mul, pair sums
+//   abi_g2.hip         beside its entry points, everything templated on G2 (BLS12-381 only); it instantiates no G1 kernel
+//   fixed_base.hpp     the group-generic launch sequences (fixed-base batch multiplication, pair sums): one copy, instantiated for
+//                      G1 by the curve units and for G2 by abi_g2.hip
+//   host_tail.hpp      host only: 64-bit-limb points of either group -- the MSM's Horner tail, affine -> XYZZ, one scalar
+//                      multiplication, a sum of points, the fixed base's window table
 //   field_<name>.hip   everything templated on one scalar field: NTT, division scan, IPA vector kernels,
 //                      column digests, the Brakedown encoder (sprs.hpp)
 // The abi units reach the templates through the two tables of plain function pointers below, one
@@ -48,12 +54,16 @@ struct NttRunner {
   virtual void run(const uint32_t* in, size_t rows, size_t in_cols, uint32_t* out) = 0;
 };
 
+// CurveOps::fixed_base / fixed_base_run<G>: results normalised around one inversion per K.  16 for pc_hip_fixed_base_batch_mul (the
+// SRS generation of KZG10::setup), 8 for the two groups of MultilinearPC (pc_hip_ml_setup, pc_hip_g2_fixed_base_batch_mul): with 16 the
+// G1 level of the setup measured 0.3 ms slower at 2^20 (profiles/EXPERIMENTS.md 000000).
+constexpr uint32_t FIXED_BASE_K_KZG = 16, FIXED_BASE_K_ML = 8;
+
 struct CurveOps {
   int aw;                 // 32-bit words per affine point
   uint32_t scalar_bits;
   MsmRunner* (*make_runner)(HipBackend& be, size_t n_max, const MsmConfig& cfg, uint32_t subs);
   void (*window_table)(HipBackend& be, const uint32_t* bases, uint32_t n, uint32_t c, uint32_t Wd, uint32_t* table, uint32_t stride);
-  void (*ec_fold)(HipBackend& be, uint32_t* key, size_t half, const uint32_t* u_mont);
   // out[i] = affine(in[i] + u * in[half + i]); table: the key's one-level fold table of width-w NAF digits (or null: GLV ladder).  out == in: in place.
   void (*ec_fold_to)(HipBackend& be, const uint32_t* in, uint32_t* out, size_t half, const uint32_t* u_mont, const uint32_t* table, uint32_t w);
   // out[i] = affine(key_lo[i] + sum_t u_t * P_t[i]) from the fold table (term t = table points [t count, (t + 1) count)); false: does not fit
@@ -62,7 +72,10 @@ struct CurveOps {
   // fold table of `count` key points for width-w NAF digits: 2^(w-2) * fold_rows rows of `count` points
   void (*fold_table_build)(HipBackend& be, const uint32_t* pts, size_t count, uint32_t w, uint32_t* table);
   uint32_t fold_rows;
-  void (*fixed_base)(HipBackend& be, const uint32_t* g, const uint32_t* scalars, size_t n, uint32_t* out);
+  // out[i] = scalars[i] * g for one affine point g (host) and n Montgomery scalars on the device; one inversion per K results (fixed_base.hpp)
+  void (*fixed_base)(HipBackend& be, const uint32_t* g, const uint32_t* scalars, size_t n, uint32_t* out, uint32_t K);
+  // out[b] = in[2b] + in[2b + 1], b < count, affine points on the device; `in` and `out` must not overlap
+  void (*pair_sums)(HipBackend& be, const uint32_t* in, size_t count, uint32_t* out);
   // ark-serialize bytes of n points (device) -> n resident affine points; returns the number of invalid points
   uint32_t (*srs_decode)(HipBackend& be, const uint8_t* bytes_dev, size_t n, int compressed, uint32_t* out);
   // n resident affine points -> their ark-serialize bytes (device buffers)

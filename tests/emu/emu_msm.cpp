@@ -9,6 +9,7 @@
 #include "../../poly_commit_amd/csrc/msm.hpp"
 #include "../../poly_commit_amd/csrc/poly.hpp"
 #include "../../poly_commit_amd/csrc/ipa.hpp"
+#include "../../poly_commit_amd/csrc/g2.hpp"
 #include "../../poly_commit_amd/csrc/hash.hpp"
 #include "../../poly_commit_amd/csrc/glv.hpp"
 #include "../../poly_commit_amd/csrc/serialize.hpp"
@@ -493,12 +494,36 @@ extern "C" void emu_srs_encode(int curve, const uint32_t* pts, uint32_t n, int c
   }
 }
 
-extern "C" void emu_fixed_base(int curve, const uint32_t* g, const uint32_t* scalars_mont, size_t n, uint32_t* out) {
+// the ladder path of fixed_base_run (fixed_base.hpp): one double-and-add per lane, each result normalised on its own
+template <class C>
+static void fixed_base_ladder(const uint32_t* g, const uint32_t* scalars_mont, size_t n, uint32_t* out) {
+  std::vector<uint32_t> res(n * pc::XyzzD<C>::WORDS + 1), scr(n * C::FqP::N + 1);
   CpuStepBackend be;
+  pc::ScalarMulStoreBody<C> body{{g, scalars_mont, 1u}, res.data()};
+  be.launch(body, n);
+  pc::XyzzBatchAffineBody<C> nb{res.data(), scr.data(), out, (uint32_t)n, 1};
+  be.launch(nb, n);
+}
+extern "C" void emu_fixed_base(int curve, const uint32_t* g, const uint32_t* scalars_mont, size_t n, uint32_t* out) {
   switch (curve) {
-    case 0: { pc::FixedBaseMulBody<pc_curve_bls12_381> b; b.scalars = scalars_mont; b.out = out; for (int i = 0; i < 24; i++) b.g[i] = g[i]; be.launch(b, n); } break;
-    case 1: { pc::FixedBaseMulBody<pc_curve_bn254> b; b.scalars = scalars_mont; b.out = out; for (int i = 0; i < 16; i++) b.g[i] = g[i]; be.launch(b, n); } break;
-    case 2: { pc::FixedBaseMulBody<pc_curve_pallas> b; b.scalars = scalars_mont; b.out = out; for (int i = 0; i < 16; i++) b.g[i] = g[i]; be.launch(b, n); } break;
+    case 0: fixed_base_ladder<pc_curve_bls12_381>(g, scalars_mont, n, out); break;
+    case 1: fixed_base_ladder<pc_curve_bn254>(g, scalars_mont, n, out); break;
+    case 2: fixed_base_ladder<pc_curve_pallas>(g, scalars_mont, n, out); break;
+  }
+}
+
+// the per-lane NAF / Jacobian ladder (FixedBaseMulBody): NafMasks::from_scalar, naf_mul and JacD on arbitrary scalars
+template <class C>
+static void fixed_base_naf(const uint32_t* g, const uint32_t* scalars_mont, size_t n, uint32_t* out) {
+  pc::FixedBaseMulBody<C> b; b.scalars = scalars_mont; b.out = out;
+  for (int i = 0; i < 2 * C::FqP::N; i++) b.g[i] = g[i];
+  CpuStepBackend be; be.launch(b, n);
+}
+extern "C" void emu_fixed_base_naf(int curve, const uint32_t* g, const uint32_t* scalars_mont, size_t n, uint32_t* out) {
+  switch (curve) {
+    case 0: fixed_base_naf<pc_curve_bls12_381>(g, scalars_mont, n, out); break;
+    case 1: fixed_base_naf<pc_curve_bn254>(g, scalars_mont, n, out); break;
+    case 2: fixed_base_naf<pc_curve_pallas>(g, scalars_mont, n, out); break;
   }
 }
 

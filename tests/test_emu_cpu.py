@@ -26,7 +26,7 @@ def emu():
         san = os.environ.get("PC_EMU_SANITIZE") == "1"
         so = os.path.join(HERE, "emu", "libemu_san.so" if san else "libemu.so")
         srcs = [os.path.join(HERE, "emu", "emu_msm.cpp")] + [
-            os.path.join(HERE, "..", "poly_commit_amd", "csrc", f) for f in ("msm.hpp", "poly.hpp", "ec.hpp", "fp32.hpp", "ipa.hpp", "glv.hpp", "serialize.hpp", "fold_table.hpp")]
+            os.path.join(HERE, "..", "poly_commit_amd", "csrc", f) for f in ("msm.hpp", "poly.hpp", "ec.hpp", "fp32.hpp", "ipa.hpp", "g2.hpp", "glv.hpp", "serialize.hpp", "fold_table.hpp")]
         if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
             flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if san else ["-O2"]
             tmp = "%s.%d.tmp" % (so, os.getpid())                      # (xdist workers may build at once: each its own file, renamed into place)
@@ -430,9 +430,9 @@ def test_ipa_round_bodies_stepped(curve):
 
 @pytest.mark.parametrize("curve", CURVES)
 def test_naf_jacobian_scalar_mul_stepped(curve):
-    """NAF recoding + Jacobian ladder (csrc/ec.hpp JacD / NafMasks, used by ec_fold and the
-    fixed-base SRS generator) against Python big ints, including the scalars whose NAF carries
-    out of the top limb."""
+    """The two per-lane ladders against Python big ints, including the scalars whose NAF carries out of the top limb: NAF recoding +
+    Jacobian ladder (csrc/ec.hpp JacD / NafMasks, what the key fold runs; stepped through FixedBaseMulBody), and the double-and-add
+    over XYZZ with its normalisation that the fixed-base multiplication runs below its table threshold."""
     fr = R.CURVES[curve]["fr"]
     p = R.FIELDS[fr]["p"]
     G = R.gen_bases(curve, 3)[2]
@@ -441,9 +441,11 @@ def test_naf_jacobian_scalar_mul_stepped(curve):
     ks = [k % p for k in ks]
     sc = O.fr_mont_array(curve, ks)
     g = O.points_to_array(curve, [G])[0]
-    out = np.zeros((len(ks), 2 * O.fq_limbs(curve)), dtype=np.uint64)
-    emu().emu_fixed_base(O.CURVES[curve], p32(g.view(np.uint32)), p32(sc.view(np.uint32)), C.c_size_t(len(ks)), p32(out.view(np.uint32)))
-    assert O.array_to_points(curve, out) == [R.ec_mul(curve, k, G) for k in ks]
+    want = [R.ec_mul(curve, k, G) for k in ks]
+    for ladder in (emu().emu_fixed_base_naf, emu().emu_fixed_base):
+        out = np.zeros((len(ks), 2 * O.fq_limbs(curve)), dtype=np.uint64)
+        ladder(O.CURVES[curve], p32(g.view(np.uint32)), p32(sc.view(np.uint32)), C.c_size_t(len(ks)), p32(out.view(np.uint32)))
+        assert O.array_to_points(curve, out) == want
 
 
 def _column_digests_hashlib(curve, ext_mont, hash_name):

@@ -1,6 +1,7 @@
 """GPU parity for InnerProductArgPC (ipa_pc/mod.rs) against the oracle's restatement: the halving rounds with
 supplied challenges, and whole openings -- combination, Fiat-Shamir transcript (Blake2s over ark-serialize
 bytes), rounds -- through both host layers above the C ABI (the C++ mirror and the Python harness)."""
+import functools
 import os
 import struct
 import subprocess
@@ -214,6 +215,47 @@ def test_fold2_from_without_a_two_level_table_is_the_two_folds(ctx):
         k2 = srs.fold2_from(n // 4, u[0], u[1])
         assert (k2.read(0, n // 4) == ref).all(), form
         k2.free()
+    srs.free()
+
+
+FOLD_MAX = 4096
+
+
+@functools.lru_cache(maxsize=None)
+def _fold_case(curve):
+    """(challenge u in Montgomery form, a pool of 2 x 4096 points, the oracle's u * pool[4096 + i] for i < 4096): computed once per
+    curve; every fold below is assembled from these products by one oracle addition per point."""
+    pool = np.ascontiguousarray(O.gen_bases(curve, 2 * FOLD_MAX))
+    u = O.gen_scalars(curve, 0xF01D, 1)
+    prod = np.zeros_like(pool[:FOLD_MAX])
+    for i in range(FOLD_MAX):
+        O.lib().orc_ec_mul(O.CURVES[curve], O.p64(pool[FOLD_MAX + i]), O.p64(u[0]), O.p64(prod[i]))
+    return O.f_to_mont(curve, 1, u)[0], pool, prod
+
+
+@pytest.mark.parametrize("curve", ["pallas", "bls12_381"])
+@pytest.mark.parametrize("half", [1, 4095, 4096])
+def test_ec_fold_in_place_and_out_of_place_match_the_oracle(ctx, curve, half):
+    """pc_hip_ec_fold (in place) and pc_hip_ec_fold_from on a key without a fold table (a new key; the source untouched): the same key,
+    the same challenge, both bit for bit the oracle's K[i] + u K[half + i] -- below and at the size from which the ladders leave
+    Jacobian results that a second kernel normalises in batches; a point at infinity in each half."""
+    u, pool, prod = _fold_case(curve)
+    lo, hi, up = pool[:half].copy(), pool[FOLD_MAX:FOLD_MAX + half].copy(), prod[:half].copy()
+    lo[half // 3] = 0
+    hi[half // 2] = 0
+    up[half // 2] = 0                                                            # u * infinity
+    key = np.ascontiguousarray(np.concatenate([lo, hi]))
+    want = np.zeros_like(lo)
+    for i in range(half):
+        O.lib().orc_ec_add(O.CURVES[curve], O.p64(up[i]), O.p64(lo[i]), O.p64(want[i]))
+    srs = ctx.upload_srs(curve, key)
+    out = srs.fold_from(half, u)
+    assert (out.read(0, half) == want).all()
+    assert (srs.read(0, 2 * half) == key).all()
+    out.free()
+    srs.ec_fold(half, u)
+    assert (srs.read(0, half) == want).all()
+    assert (srs.read(half, half) == key[half:]).all()                            # the upper half is left as it was
     srs.free()
 
 

@@ -2,6 +2,8 @@
 commit = MSM(powers, coeffs) (kzg10/mod.rs:157-210), open = witness polynomial (:217-240)
 + MSM (:243-284), against the CPU oracle's restatement, and the reference's own property
 checks: commitment homomorphism (kzg10/mod.rs:520-544) and p(z) = q(z)(z - z0) + p(z0)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -113,6 +115,55 @@ def test_true_srs_end_to_end_trapdoor_check(ctx, curve, d):
     rhs = pc.point_mul(curve, w, O.fr_mont_array(curve, [(b - zi) % p])[0])
     assert (lhs == rhs).all() and lhs.any()
     srs.free()
+
+
+FB_BLOCK = 4097
+
+
+@functools.lru_cache(maxsize=None)
+def _fixed_base_block(curve):
+    """(canonical scalars, oracle products k * g) of one 4097-long block: 0, 1, r - 1 and scalars whose signed radix-256 recoding meets
+    the digits 128 (kept) and 129 (-127 and a carry) in the lowest, in a middle, in every and in the top window, then random ones."""
+    r = _int_fr(curve)
+    top = (r.bit_length() - 1) // 8                    # the highest byte a scalar below r can fill
+    special = [r - 1, 0, 1, 128, 129, 128 << 8 | 129, 129 << 128, sum(128 << (8 * i) for i in range(top)), sum(129 << (8 * i) for i in range(top)),
+               r - 128, r - 129, (1 << (8 * top)) - 1]
+    ks = O.ints_to_limbs(special, 4)
+    ks = np.ascontiguousarray(np.concatenate([ks, O.gen_scalars(curve, 0xF1BA5E, FB_BLOCK - len(special))]))
+    g = O.gen_bases(curve, 1)[0]
+    want = np.zeros((FB_BLOCK, 2 * O.fq_limbs(curve)), dtype=np.uint64)
+    for i in range(FB_BLOCK):
+        O.lib().orc_ec_mul(O.CURVES[curve], O.p64(g), O.p64(ks[i]), O.p64(want[i]))
+    return g, ks, want
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_fixed_base_batch_mul_both_paths_and_past_the_slab(ctx, curve):
+    """pc_hip_fixed_base_batch_mul bit for bit the oracle's k * g on both sides of the switch from the per-lane ladder to the window
+    table (4096 scalars), for a base at infinity, and one scalar past the slab in which the table path normalises its results."""
+    import torch
+    g, ks, want = _fixed_base_block(curve)
+    aw = want.shape[1]
+    block = torch.from_numpy(O.f_to_mont(curve, 1, ks).view(np.int64)).cuda()
+    out = torch.empty((FB_BLOCK, aw), dtype=torch.int64, device="cuda")
+    for n in (1, 4095, 4096, 4097):
+        out.fill_(-1)
+        ctx.fixed_base_batch_mul(curve, g, block.data_ptr(), n, out.data_ptr())
+        got = out.cpu().numpy().view(np.uint64)
+        assert (got[:n] == want[:n]).all(), n
+        assert (got[n:] == np.uint64(0xFFFFFFFFFFFFFFFF)).all(), n           # nothing written behind the n results
+    block_out = out.clone()                                                     # the 4097 products, verified above
+    for n in (4095, 4096):
+        out.fill_(-1)
+        ctx.fixed_base_batch_mul(curve, np.zeros(aw, dtype=np.uint64), block.data_ptr(), n, out.data_ptr())
+        assert not out[:n].any(), n                                             # k * infinity = infinity, encoded as zeros
+    n = (1 << 18) + 1
+    idx = torch.arange(n, device="cuda") % FB_BLOCK
+    big = torch.empty((n, aw), dtype=torch.int64, device="cuda")
+    ctx.fixed_base_batch_mul(curve, g, block[idx].contiguous().data_ptr(), n, big.data_ptr())
+    assert torch.equal(big, block_out[idx])
+    last_of_slab, first_of_next = (big[i].cpu().numpy().view(np.uint64) for i in ((1 << 18) - 1, 1 << 18))
+    assert (last_of_slab == want[((1 << 18) - 1) % FB_BLOCK]).all() and (first_of_next == want[(1 << 18) % FB_BLOCK]).all()
 
 
 def test_sharded_engine_world1_matches_oracle(ctx):

@@ -111,6 +111,43 @@ print("ok")
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr[-3000:]
 
 
+@pytest.mark.parametrize("group", ["g1", "g2"])
+def test_key_from_the_strided_rust_layout_reads_back_packed(ctx, group):
+    """pc_hip_srs_upload / pc_hip_g2_srs_upload from Rust's Affine{x, y, infinity} (stride = point bytes + 8, the flag byte behind the
+    coordinates) and pc_hip_[g2_]srs_read: the key holds the packed points, the flagged ones as zeros, exactly like a packed upload of
+    them; a range that leaves the key -- also one whose offset + count wraps -- is refused."""
+    import ctypes as C
+    curve, n, flagged = "bls12_381", 37, (4, 36)
+    if group == "g1":
+        pts = O.gen_bases(curve, n).view(np.uint8)
+        upload, read = ctx.upload_srs, ctx.lib.pc_hip_srs_read
+    else:
+        from harness import g2ref as G
+        pts = np.ascontiguousarray(G.points_array(G.fixed_base(G.generator()).mul_many(range(1, n + 1)))).view(np.uint8).reshape(n, -1)
+        upload, read = ctx.upload_g2_srs, ctx.lib.pc_hip_g2_srs_read
+    pb = pts.shape[1]
+    rust = np.zeros((n, pb + 8), dtype=np.uint8)
+    rust[:, :pb] = pts
+    want = pts.copy()
+    for i in flagged:
+        rust[i, :pb] = 0xA5                            # garbage coordinates, flagged as the identity
+        rust[i, pb] = 1
+        want[i] = 0
+    strided, packed = upload(curve, rust, n=n, stride_bytes=pb + 8), upload(curve, want.view(np.uint64) if group == "g1" else want)
+    try:
+        got = strided.read(0, n).view(np.uint8).reshape(n, pb)
+        assert (got == want).all() and (packed.read(0, n).view(np.uint8).reshape(n, pb) == want).all()
+        assert (strided.read(n - 1, 1).view(np.uint8).reshape(-1) == want[n - 1]).all() and strided.read(n, 0).size == 0
+        buf = np.zeros((n, pb), dtype=np.uint8)
+        for offset, count in ((n, C.c_size_t(-1).value), (1, n)):
+            rc = read(ctx.h, strided.h, C.c_size_t(offset), C.c_size_t(count), C.c_void_p(buf.ctypes.data))
+            assert rc == -1, (offset, count)                       # PC_ERR_INVALID_ARG
+        assert not buf.any()
+    finally:
+        strided.free()
+        packed.free()
+
+
 def test_trim_gives_back_the_second_buffers_of_host_calls_in_parts():
     """A blocking MSM on HOST scalars above the split size allocates a second sort output and bucket array on its pipeline
     (MsmPlan::begin_parts); pc_hip_ctx_trim releases them (advisor, round 5) and the next host call brings them back."""
