@@ -7,8 +7,8 @@
  *
  * Conventions (identical to arkworks' in-memory representations, so buffers cross the FFI
  * without conversion):
- *   - field element: little-endian limbs, Montgomery form, 32 bytes (Fr of all three curves,
- *     Fq of BN254 / Pallas) or 48 bytes (Fq of BLS12-381)       [ark-ff Fp<MontBackend>]
+ *   - field element: little-endian limbs, Montgomery form, 32 bytes (Fr of all four curves,
+ *     Fq of BN254 / Pallas) or 48 bytes (Fq of BLS12-381 / BLS12-377)   [ark-ff Fp<MontBackend>]
  *   - "bigint" scalar: canonical residue, 32 bytes LE               [F::into_bigint()]
  *   - affine point: x || y (Montgomery).  With stride == 2*sizeof(Fq) the point at infinity
  *     is encoded as (0,0); with a larger stride (Rust `Affine{x,y,infinity:bool}`, 104 / 72
@@ -30,7 +30,8 @@ typedef struct pc_ctx pc_ctx;
 typedef struct pc_srs pc_srs;
 typedef struct pc_job pc_job;
 
-typedef enum { PC_CURVE_BLS12_381 = 0, PC_CURVE_BN254 = 1, PC_CURVE_PALLAS = 2 } pc_curve;
+/* PC_CURVE_BLS12_377: G1 and Fr only -- the pc_hip_g2_* and pc_hip_ml_* entry points return PC_ERR_INVALID_ARG for it. */
+typedef enum { PC_CURVE_BLS12_381 = 0, PC_CURVE_BN254 = 1, PC_CURVE_PALLAS = 2, PC_CURVE_BLS12_377 = 3 } pc_curve;
 typedef enum { PC_SCALARS_CANONICAL = 0, PC_SCALARS_MONTGOMERY = 1 } pc_scalar_form;
 typedef enum { PC_MEM_HOST = 0, PC_MEM_DEVICE = 1 } pc_mem;
 
@@ -67,10 +68,10 @@ void pc_hip_srs_free(pc_srs* srs);
  * powers_of_g first: poly-commit/src/kzg10/data_structures.rs:57-77; deserialisation :80-112) and what an IPA key is
  * (ipa_pc/data_structures.rs:17-36).  At most max_points points (0 = all) are decoded ON THE DEVICE (compressed points:
  * y = (x^3 + b)^((p+1)/4) for BLS12-381 and BN254) into a resident SRS; *out_bytes_consumed = 8 + len * point size, where
- * the next field of the structure starts.  Pallas (p = 1 mod 2^32) takes its square roots by Tonelli-Shanks.  Every decoded point is checked to be on the curve (PC_ERR_INVALID_ARG
+ * the next field of the structure starts.  Pallas (p = 1 mod 2^32) and BLS12-377 (p = 1 mod 2^46) take their square roots by Tonelli-Shanks.  Every decoded point is checked to be on the curve (PC_ERR_INVALID_ARG
  * otherwise); the subgroup check of Validate::Yes is the verifier-side `check()` and is not repeated here.
  * Point encodings: host/transcript.hpp / csrc/serialize.hpp (ark-ec's generic short-Weierstrass flags; the zcash
- * encoding for BLS12-381). */
+ * encoding for BLS12-381; BLS12-377 takes the generic form: 48 / 96 bytes, flags in the top bits of the last byte). */
 int pc_hip_srs_load_serialized(pc_ctx* ctx, pc_curve curve, const void* bytes, size_t n_bytes, int compressed,
                                size_t max_points, pc_srs** out, size_t* out_points, size_t* out_bytes_consumed);
 /* The inverse: `count` resident points from `offset` on as the ark-serialize image of a Vec<G1Affine> (u64 LE length, then the
@@ -83,7 +84,8 @@ int pc_hip_srs_serialize(pc_ctx* ctx, const pc_srs* srs, size_t offset, size_t c
  * in this order (kzg10/data_structures.rs:57-77; deserialisation :80-112).  out = {offset of powers_of_g, its length, offset of
  * powers_of_gamma_g, its length, offset of h, offset of beta_h, offset of neg_powers_of_h, its length, total bytes}; offsets
  * point at the u64 length prefixes (map entries: u64 LE key, then the point).  The committer's half goes to the device with
- * pc_hip_srs_load_serialized(bytes + out[0]); the G2 fields stay with the verifier-side Rust.  BLS12-381 and BN254. */
+ * pc_hip_srs_load_serialized(bytes + out[0]); the G2 fields stay with the verifier-side Rust.  The pairing curves: BLS12-381, BN254 and BLS12-377 (G2 points of 96 / 192, 64 / 128
+ * and 96 / 192 bytes). */
 int pc_hip_universal_params_layout(pc_curve curve, const void* bytes, size_t n_bytes, int compressed, size_t out[9]);
 /* Optional, once per committer key (same place as the upload, i.e. `trim`): build the window
  * table T[w][i] = 2^(c w) * bases[i] in HBM, (bits/c + 1) x the size of the SRS (BLS12-381: every 96-byte point in its
@@ -95,7 +97,7 @@ int pc_hip_universal_params_layout(pc_curve curve, const void* bytes, size_t n_b
  * VariableBaseMSM has no fixed-base state. */
 int pc_hip_srs_precompute(pc_ctx* ctx, pc_srs* srs, unsigned window_bits, size_t min_pairs);
 /* The same with the form of the table chosen by the caller.  PC_HIP_TABLE_GLV: the table holds only the windows of the ~128-bit halves of
- * the GLV split k = k1 + k2*lambda (BLS12-381, BN254 and Pallas all have the j = 0 endomorphism phi(x, y) = (beta x, y)): HALF the
+ * the GLV split k = k1 + k2*lambda (all four curves have the j = 0 endomorphism phi(x, y) = (beta x, y)): HALF the
  * memory and build time (12.9 instead of 25.8 GB for a 2^24-point BLS12-381 key); every scalar is split on the device, the digits of
  * k2 go to a second bucket set with the SAME table points, and phi is applied once to that set's reduced sum -- the same number of
  * bucket additions, one more bucket set to reduce (more below 2^22, where the reduction weighs more).  The split runs once per
@@ -490,7 +492,8 @@ int pc_hip_srs_read(pc_ctx* ctx, const pc_srs* srs, size_t offset, size_t count,
  * 192 is arkworks' infinity flag, as for pc_hip_srs_upload.  A pc_g2_srs is a typed handle of its own: no G1 entry point can be
  * handed a G2 key.  It belongs to its context: counted by pc_hip_ctx_bytes_resident (out[0] and out[5]) and released by
  * pc_hip_shutdown if the caller has not freed it (the handle then only remains to be freed).  Only PC_CURVE_BLS12_381 is built
- * (the curve the reference instantiates, multilinear_pc/mod.rs:247): BN254 and Pallas give PC_ERR_UNSUPPORTED.
+ * (the curve the reference instantiates, multilinear_pc/mod.rs:247): BN254 and Pallas give PC_ERR_UNSUPPORTED, BLS12-377 (whose Fq2 is
+ * Fq[u] / (u^2 + 5), not the u^2 + 1 of csrc/fp2.hpp) PC_ERR_INVALID_ARG.
  * The G2 MSM is table-free: no window table, no GLV, no captured launch graphs, no host-parts split. */
 typedef struct pc_g2_srs pc_g2_srs;
 /* The residency hook of MultilinearPC::trim (multilinear_pc/mod.rs:91-111: powers_of_h copied by value at :98). */

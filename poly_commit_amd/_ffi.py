@@ -6,8 +6,8 @@ import os
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CURVES = {"bls12_381": 0, "bn254": 1, "pallas": 2}
-FQ_BYTES = {"bls12_381": 48, "bn254": 32, "pallas": 32}
+CURVES = {"bls12_381": 0, "bn254": 1, "pallas": 2, "bls12_377": 3}
+FQ_BYTES = {"bls12_381": 48, "bn254": 32, "pallas": 32, "bls12_377": 48}
 PC_MEM_HOST, PC_MEM_DEVICE = 0, 1
 PC_SCALARS_CANONICAL, PC_SCALARS_MONTGOMERY = 0, 1
 

@@ -14,8 +14,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["abi_ctx.hip", "abi_srs.hip", "abi_msm.hip", "abi_poly.hip", "abi_ipa.hip", "abi_lincode.hip", "abi_g2.hip", "group.hip", "hash_tu.hip",
-           "curve_bls12_381.hip", "curve_bn254.hip", "curve_pallas.hip",
-           "field_bls12_381.hip", "field_bn254.hip", "field_pallas.hip"]
+           "curve_bls12_381.hip", "curve_bn254.hip", "curve_pallas.hip", "curve_bls12_377.hip",
+           "field_bls12_381.hip", "field_bn254.hip", "field_pallas.hip", "field_bls12_377.hip"]
 # PC_HIP_VARIANT=name builds an alternative library libpc_hip_<name>.so (own object cache) from the same sources with
 # PC_HIP_CXXFLAGS -- kernel tuning experiments; load it with PC_HIP_LIB=<path>
 _VARIANT = os.environ.get("PC_HIP_VARIANT", "")
@@ -24,12 +24,14 @@ OUT = os.path.join(HERE, "libpc_hip" + ("_" + _VARIANT if _VARIANT else "") + ".
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 MAX_JOBS = 16
 
-# the probe: (source, PROBE_SET or None); a unit with a set compiles once per curve (tests/hip/probe_sets.hpp)
+# the probe: (source, PROBE_SET or None); a unit with a set compiles once per curve (tests/hip/probe_sets.hpp), the others name
+# their types themselves
 PROBE_DIR = os.path.join(os.path.dirname(HERE), "tests", "hip")
 PROBE_OBJ = os.path.join(PROBE_DIR, "_obj")
 PROBE_OUT = os.path.join(PROBE_DIR, "libpc_probe.so")
 PROBE_UNITS = ([("probe_field.hip", k) for k in range(3)] + [("probe_curve.hip", k) for k in range(4)] +
-               [("probe_halfadd.hip", k) for k in range(3)] + [("probe_fq30.hip", None), ("probe_chain30.hip", None)])
+               [("probe_halfadd.hip", k) for k in range(3)] + [("probe_fq30.hip", None), ("probe_chain30.hip", None)] +
+               [("probe_field_bls12_377.hip", None), ("probe_curve_bls12_377.hip", None)])
 
 
 def _newest_header():

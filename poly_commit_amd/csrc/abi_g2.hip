@@ -83,7 +83,8 @@ using pc::G2_AW;
 using pc::FR_W;
 
 static int g2_curve_check(pc_curve curve) {
-  if ((int)curve < 0 || (int)curve > 2) return PC_ERR_INVALID_ARG;
+  // BLS12-377's Fq2 is Fq[u] / (u^2 + 5) and fp2.hpp is written for u^2 + 1: no G2 of it here, and the id is refused like an unknown one
+  if (!pc_known_curve(curve) || curve == PC_CURVE_BLS12_377) return PC_ERR_INVALID_ARG;
   return curve == PC_CURVE_BLS12_381 ? PC_OK : PC_ERR_UNSUPPORTED;
 }
 

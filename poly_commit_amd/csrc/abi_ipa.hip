@@ -7,7 +7,7 @@ extern "C" {
 
 // ---- IPA round kernels --------------------------------------------------------------------
 int pc_hip_fr_fold(pc_ctx* ctx, pc_curve field_of, void* lo_dev, const void* hi_dev, size_t n_half, const void* s_host) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !s_host || (n_half && (!lo_dev || !hi_dev))) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !s_host || (n_half && (!lo_dev || !hi_dev))) return PC_ERR_INVALID_ARG;
   if (n_half >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
@@ -16,7 +16,7 @@ int pc_hip_fr_fold(pc_ctx* ctx, pc_curve field_of, void* lo_dev, const void* hi_
   });
 }
 int pc_hip_fr_dot(pc_ctx* ctx, pc_curve field_of, const void* a_dev, const void* b_dev, size_t n, void* out_host) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !out_host || (n && (!a_dev || !b_dev))) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !out_host || (n && (!a_dev || !b_dev))) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
@@ -26,7 +26,7 @@ int pc_hip_fr_dot(pc_ctx* ctx, pc_curve field_of, const void* a_dev, const void*
 }
 int pc_hip_ipa_fold_dots(pc_ctx* ctx, pc_curve field_of, void* coeffs_dev, void* z_dev, size_t m, const void* u_host, const void* u_inv_host,
                          void* out_dots_host) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !coeffs_dev || !z_dev || !out_dots_host || !m || (m & (m - 1))) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !coeffs_dev || !z_dev || !out_dots_host || !m || (m & (m - 1))) return PC_ERR_INVALID_ARG;
   if ((u_host != nullptr) != (u_inv_host != nullptr)) return PC_ERR_INVALID_ARG;
   if (m >= (1ull << 31)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -37,7 +37,7 @@ int pc_hip_ipa_fold_dots(pc_ctx* ctx, pc_curve field_of, void* coeffs_dev, void*
   });
 }
 int pc_hip_fr_powers(pc_ctx* ctx, pc_curve field_of, const void* z_host, size_t n, void* out_dev) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !z_host || (n && !out_dev)) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !z_host || (n && !out_dev)) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
@@ -47,7 +47,7 @@ int pc_hip_fr_powers(pc_ctx* ctx, pc_curve field_of, const void* z_host, size_t 
 }
 int pc_hip_ipa_key_scalars(pc_ctx* ctx, pc_curve field_of, const void* coeffs_dev, size_t m, void* s_dev, size_t n0,
                            const void* fold_u_host, size_t fold_m, void* out_l_dev, void* out_r_dev) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !s_dev || !n0 || (n0 & (n0 - 1))) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !s_dev || !n0 || (n0 & (n0 - 1))) return PC_ERR_INVALID_ARG;
   if (fold_u_host && (fold_m < 2 || (fold_m & (fold_m - 1)) || fold_m > n0)) return PC_ERR_INVALID_ARG;
   if ((out_l_dev != nullptr) != (out_r_dev != nullptr)) return PC_ERR_INVALID_ARG;
   if (out_l_dev && (!coeffs_dev || m < 2 || (m & (m - 1)) || m > n0)) return PC_ERR_INVALID_ARG;
@@ -261,13 +261,13 @@ int pc_hip_ipa_open_rounds(pc_ctx* ctx, const pc_srs* comm_key, void* coeffs_dev
 }
 
 int pc_hip_point_mul(pc_curve curve, const void* point_xy, const void* scalar_mont, void* out_xy) {
-  if ((int)curve < 0 || (int)curve > 2 || !point_xy || !scalar_mont || !out_xy) return PC_ERR_INVALID_ARG;
+  if (!pc_known_curve(curve) || !point_xy || !scalar_mont || !out_xy) return PC_ERR_INVALID_ARG;
   pc::curve_ops(curve).point_mul((const uint32_t*)point_xy, (const uint32_t*)scalar_mont, (uint32_t*)out_xy);
   return PC_OK;
 }
 int pc_hip_fixed_base_batch_mul(pc_ctx* ctx, pc_curve curve, const void* g_xy_host, const void* scalars_dev, size_t n,
                                 void* out_points_dev) {
-  if (!ctx || (int)curve < 0 || (int)curve > 2 || !g_xy_host || (n && (!scalars_dev || !out_points_dev))) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(curve) || !g_xy_host || (n && (!scalars_dev || !out_points_dev))) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {

@@ -36,7 +36,7 @@ extern "C" {
 int pc_hip_brakedown_code_create(pc_ctx* ctx, pc_curve field_of, size_t msg_len, size_t codeword_len, size_t n_levels, const size_t* dims,
                                  const size_t* ind_ptr, const uint32_t* col_ind, const void* val, size_t nnz, pc_lincode** out) {
   if (out) *out = nullptr;
-  if (!ctx || !out || (int)field_of < 0 || (int)field_of > 2 || (nnz && !val)) return PC_ERR_INVALID_ARG;
+  if (!ctx || !out || !pc_known_curve(field_of) || (nnz && !val)) return PC_ERR_INVALID_ARG;
   // everything about the arrays is decided on the host, before the device sees any of it
   pc::BrakedownLayout L;
   if (pc::brakedown_validate(msg_len, codeword_len, n_levels, dims, ind_ptr, col_ind, nnz, &L) != 0) return PC_ERR_INVALID_ARG;

@@ -273,7 +273,7 @@ int pc_hip_msm_many(pc_ctx* ctx, pc_srs* srs, size_t base_offset, const void* sc
     const size_t pb = (size_t)srs->aw * 4;
     if (!n_msms) return (int)PC_OK;
     if (!m) { memset(out_xy, 0, n_msms * pb); if (out_is_infinity) for (size_t k = 0; k < n_msms; k++) out_is_infinity[k] = 1; return (int)PC_OK; }
-    const uint32_t bits = srs->curve == PC_CURVE_BN254 ? 254u : 255u;
+    const uint32_t bits = pc::curve_ops(srs->curve).scalar_bits;      // 255 / 254 / 255 / 253
     const uint32_t c = pc::msm_choose_table_c(m, bits, 0), Wd = pc::msm_num_windows(bits, c);
     if ((uint64_t)n_msms * m * Wd >= (1ull << 31) || ((uint64_t)n_msms << (c - 1)) >= (1ull << 31)) return (int)PC_ERR_TOO_LARGE;
     pc_srs::Many& M = srs->many;
@@ -305,7 +305,7 @@ int pc_hip_msm_many(pc_ctx* ctx, pc_srs* srs, size_t base_offset, const void* sc
 }
 
 int pc_hip_points_sum(pc_curve curve, const void* points_xy, size_t count, void* out_xy) {
-  if ((int)curve < 0 || (int)curve > 2 || !out_xy || (count && !points_xy)) return PC_ERR_INVALID_ARG;
+  if (!pc_known_curve(curve) || !out_xy || (count && !points_xy)) return PC_ERR_INVALID_ARG;
   pc::curve_ops(curve).points_sum((const uint32_t*)points_xy, count, (uint32_t*)out_xy);
   return PC_OK;
 }

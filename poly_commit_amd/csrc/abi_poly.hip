@@ -173,8 +173,8 @@ extern "C" {
 
 int pc_hip_ntt_batch(pc_ctx* ctx, pc_curve field_of, const void* in, pc_mem where_in, size_t rows, size_t in_cols,
                      unsigned log_n, void* out, pc_mem where_out) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || (rows && (!in || !out))) return PC_ERR_INVALID_ARG;
-  const unsigned max_lg = field_of == PC_CURVE_BN254 ? 28 : 32;
+  if (!ctx || !pc_known_curve(field_of) || (rows && (!in || !out))) return PC_ERR_INVALID_ARG;
+  const unsigned max_lg = field_of == PC_CURVE_BN254 ? 28 : 32;      // BN254: the two-adicity; the others (32, 32, 47): the 32-bit indices
   if (log_n > max_lg) return PC_ERR_TOO_LARGE;
   if (log_n > PC_HIP_NTT_MAX_LOG_N) return PC_ERR_UNSUPPORTED;   // two LDS-staged passes: one factor must fit the 160 KB LDS
   if (in_cols > ((size_t)1 << log_n)) return PC_ERR_INVALID_ARG;
@@ -212,7 +212,7 @@ int pc_hip_last_ntt_phases_ms(const pc_ctx* ctx, float out[2]) {
 
 int pc_hip_poly_eval(pc_ctx* ctx, pc_curve field_of, const void* coeffs, pc_mem where_in, size_t n, const void* z_host,
                      void* out_host) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !z_host || !out_host || (n && !coeffs)) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !z_host || !out_host || (n && !coeffs)) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
@@ -225,7 +225,7 @@ int pc_hip_poly_eval(pc_ctx* ctx, pc_curve field_of, const void* coeffs, pc_mem 
 
 int pc_hip_poly_div_scan(pc_ctx* ctx, pc_curve field_of, const void* coeffs, pc_mem where_in, size_t n, const void* z_host,
                          const void* carry_in_host, void* out, pc_mem where_out) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !z_host || (n && (!coeffs || !out))) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !z_host || (n && (!coeffs || !out))) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
@@ -241,7 +241,7 @@ int pc_hip_poly_div_scan(pc_ctx* ctx, pc_curve field_of, const void* coeffs, pc_
 
 int pc_hip_column_hash(pc_ctx* ctx, pc_curve field_of, const void* ext_mat, pc_mem where_in, size_t rows, size_t n_cols,
                        pc_hash hash, void* out_digests, pc_mem where_out) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || ((int)hash != PC_HASH_SHA256 && (int)hash != PC_HASH_BLAKE2S) ||
+  if (!ctx || !pc_known_curve(field_of) || ((int)hash != PC_HASH_SHA256 && (int)hash != PC_HASH_BLAKE2S) ||
       (rows && n_cols && (!ext_mat || !out_digests))) return PC_ERR_INVALID_ARG;
   if (rows >= (1ull << 32) || n_cols >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -261,7 +261,7 @@ int pc_hip_column_hash(pc_ctx* ctx, pc_curve field_of, const void* ext_mat, pc_m
 
 int pc_hip_column_hash_part(pc_ctx* ctx, pc_curve field_of, pc_hash hash, const void* ext_slab_dev, size_t rows, size_t n_cols, size_t rows_total,
                             size_t col0, size_t cols, int first, int last, void* state_dev, void* out_digests_dev) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || ((int)hash != PC_HASH_SHA256 && (int)hash != PC_HASH_BLAKE2S)) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || ((int)hash != PC_HASH_SHA256 && (int)hash != PC_HASH_BLAKE2S)) return PC_ERR_INVALID_ARG;
   if (rows >= (1ull << 32) || n_cols >= (1ull << 32) || rows_total >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   if (col0 > n_cols || cols > n_cols - col0 || rows > rows_total || (rows && cols && !ext_slab_dev)) return PC_ERR_INVALID_ARG;
   if (cols && ((!(first && last) && !state_dev) || (last && !out_digests_dev))) return PC_ERR_INVALID_ARG;
@@ -278,7 +278,7 @@ int pc_hip_column_hash_part(pc_ctx* ctx, pc_curve field_of, pc_hash hash, const 
 
 int pc_hip_witness_poly(pc_ctx* ctx, pc_curve field_of, const void* coeffs, pc_mem where_in, size_t n, const void* z_host,
                         void* out, pc_mem where_out) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || !z_host || (n && !coeffs) || (n > 1 && !out)) return PC_ERR_INVALID_ARG;
+  if (!ctx || !pc_known_curve(field_of) || !z_host || (n && !coeffs) || (n > 1 && !out)) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
@@ -299,7 +299,7 @@ int pc_hip_ligero_commit(pc_ctx* ctx, pc_curve field_of, const void* mat, pc_mem
     return PC_ERR_INVALID_ARG;
   if (log_n > PC_HIP_NTT_MAX_LOG_N) return PC_ERR_UNSUPPORTED;
   auto known = [](pc_hash h) { return (int)h == PC_HASH_SHA256 || (int)h == PC_HASH_BLAKE2S; };
-  if ((int)field_of < 0 || (int)field_of > 2 || !known(col_hash) || !known(tree_hash)) return PC_ERR_INVALID_ARG;
+  if (!pc_known_curve(field_of) || !known(col_hash) || !known(tree_hash)) return PC_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   const size_t N = (size_t)1 << log_n;
   if (where_in == PC_MEM_HOST && ext_out && where_ext == PC_MEM_HOST && rows < (1ull << 32))
@@ -386,7 +386,7 @@ int pc_hip_matrix_columns(pc_ctx* ctx, const void* mat_dev, size_t rows, size_t 
 
 int pc_hip_fr_lincomb(pc_ctx* ctx, pc_curve field_of, const void* const* polys, pc_mem where_in, const size_t* lens,
                       size_t k, const void* xi_host, void* out, pc_mem where_out, size_t n_out) {
-  if (!ctx || (int)field_of < 0 || (int)field_of > 2 || (k && (!polys || !lens || !xi_host)) || (n_out && !out))
+  if (!ctx || !pc_known_curve(field_of) || (k && (!polys || !lens || !xi_host)) || (n_out && !out))
     return PC_ERR_INVALID_ARG;
   if (n_out >= (1ull << 32) || k >= (1ull << 20)) return PC_ERR_TOO_LARGE;
   size_t total = 0;

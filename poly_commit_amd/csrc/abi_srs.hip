@@ -6,7 +6,7 @@ extern "C" {
 
 int pc_hip_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t n, size_t stride_bytes, pc_mem where,
                       pc_srs** out) {
-  if (!ctx || !out || (!bases && n) || (int)curve < 0 || (int)curve > 2) return PC_ERR_INVALID_ARG;
+  if (!ctx || !out || (!bases && n) || !pc_known_curve(curve)) return PC_ERR_INVALID_ARG;
   const size_t pb = 2 * (size_t)fq_bytes(curve);
   if (stride_bytes == 0) stride_bytes = pb;
   if (stride_bytes < pb) return PC_ERR_INVALID_ARG;
@@ -39,14 +39,14 @@ int pc_hip_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t n, 
 
 static size_t g1_point_bytes(pc_curve curve, int compressed) {
   const size_t fb = (size_t)fq_bytes(curve);
-  const size_t bits = curve == PC_CURVE_BLS12_381 ? 381 : curve == PC_CURVE_BN254 ? 254 : 255;
+  const size_t bits = curve == PC_CURVE_BLS12_381 ? 381 : curve == PC_CURVE_BN254 ? 254 : curve == PC_CURVE_BLS12_377 ? 377 : 255;
   const size_t yb = (bits + 2 + 7) / 8;
   return curve == PC_CURVE_BLS12_381 ? (compressed ? fb : 2 * fb) : (compressed ? yb : fb + yb);
 }
 
 int pc_hip_srs_load_serialized(pc_ctx* ctx, pc_curve curve, const void* bytes, size_t n_bytes, int compressed, size_t max_points,
                                pc_srs** out, size_t* out_points, size_t* out_bytes_consumed) {
-  if (!ctx || !out || !bytes || (int)curve < 0 || (int)curve > 2) return PC_ERR_INVALID_ARG;
+  if (!ctx || !out || !bytes || !pc_known_curve(curve)) return PC_ERR_INVALID_ARG;
   *out = nullptr;
   if (n_bytes < 8) return PC_ERR_INVALID_ARG;
   const size_t fb = (size_t)fq_bytes(curve), pbytes = g1_point_bytes(curve, compressed);
@@ -97,10 +97,11 @@ int pc_hip_universal_params_layout(pc_curve curve, const void* bytes, size_t n_b
   // kzg10::UniversalParams, CanonicalSerialize order (kzg10/data_structures.rs:57-77):
   //   powers_of_g: Vec<G1Affine> | powers_of_gamma_g: BTreeMap<usize, G1Affine> | h: G2Affine | beta_h: G2Affine |
   //   neg_powers_of_h: BTreeMap<usize, G2Affine>        (Vec / BTreeMap: u64 LE length first; map entries: u64 LE key, value)
-  if (!bytes || !out || ((int)curve != PC_CURVE_BLS12_381 && (int)curve != PC_CURVE_BN254)) return PC_ERR_INVALID_ARG;   // pairing curves only
+  if (!bytes || !out || ((int)curve != PC_CURVE_BLS12_381 && (int)curve != PC_CURVE_BN254 && (int)curve != PC_CURVE_BLS12_377)) return PC_ERR_INVALID_ARG;   // pairing curves only
   const size_t g1 = g1_point_bytes(curve, compressed);
-  // G2 over Fq2: BLS12-381 (zcash): 96 / 192 bytes; BN254 (generic SW over Fq2, flags in the spare bits of the last byte): 64 / 128
-  const size_t g2 = curve == PC_CURVE_BLS12_381 ? (compressed ? 96 : 192) : (compressed ? 64 : 128);
+  // G2 over Fq2: BLS12-381 (zcash): 96 / 192 bytes; BN254 and BLS12-377 (generic SW over Fq2, flags in the spare bits of the last byte):
+  // 64 / 128 and 96 / 192
+  const size_t fb = (size_t)fq_bytes(curve), g2 = compressed ? 2 * fb : 4 * fb;
   const uint8_t* p = (const uint8_t*)bytes;
   size_t at = 0;
   auto take_len = [&](uint64_t& v) { if (n_bytes - at < 8) return false; memcpy(&v, p + at, 8); at += 8; return true; };

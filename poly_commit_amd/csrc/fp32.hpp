@@ -405,9 +405,10 @@ struct Fd {
   // With R >= 4p a Montgomery product of operands in [0, 2p] is below (4p^2 + pR)/R <= 2p WITHOUT the final conditional
   // subtraction: inside a long chain of multiplications (the mixed addition of the bucket accumulation: 9 multiplier calls)
   // values are kept in [0, 2p) and canonicalised only where they leave the chain; additive operations then work modulo 2p
-  // (their results, up to 4p, must fit N limbs: the same bound).  LAZY_OK: BLS12-381 Fq (381 bits in 384) and BN254 Fq
-  // (254 in 256; R = 5.29p); Pallas' p = 2^254 + ... has 4p > 2^256 and keeps the canonical path.
-  // The fused a*b + c*d is below (8p^2 + pR)/R: below 2p only when R >= 8p (LAZY_FUSED_OK: BLS12-381); with 4p <= R < 8p it is
+  // (their results, up to 4p, must fit N limbs: the same bound).  LAZY_OK: BLS12-381 Fq (381 bits in 384), BLS12-377 Fq
+  // (377 in 384; R = 152p) and BN254 Fq (254 in 256; R = 5.29p); Pallas' p = 2^254 + ... has 4p > 2^256 and keeps the canonical path.
+  // All three flags are functions of the modulus alone.
+  // The fused a*b + c*d is below (8p^2 + pR)/R: below 2p only when R >= 8p (LAZY_FUSED_OK: the two BLS12 curves); with 4p <= R < 8p it is
   // below 3p and keeps its ONE conditional subtraction, which brings it below 2p again (not necessarily below p).
   // LAZY_STORE_OK (R >= 9p): lazily reduced coordinates may also LEAVE the accumulation as they are -- the consumers' formulas
   // (XyzzD::add / dbl, canonical multiplier) start with products of loaded coordinates, except dbl()'s U = 2Y (one conditional

@@ -14,6 +14,7 @@ template <class C> struct GlvOf;
 template <> struct GlvOf<pc_curve_bls12_381> { typedef pc_glv_bls12_381 T; };
 template <> struct GlvOf<pc_curve_bn254> { typedef pc_glv_bn254 T; };
 template <> struct GlvOf<pc_curve_pallas> { typedef pc_glv_pallas T; };
+template <> struct GlvOf<pc_curve_bls12_377> { typedef pc_glv_bls12_377 T; };
 
 struct GlvSplit { uint32_t k1[5], k2[5]; uint32_t neg1, neg2; };   // sign-magnitude, 160-bit magnitudes
 

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "../../include/pc_hip.h"
 #include "host_tail.hpp"
+#include "curves.hpp"
 
 // Persistent threads per device, each with a FIFO of tasks (round 2 spawned and joined N std::threads per call): the WORKER queues
 // work on the device (every group call hands its per-device part to it), the COPIER brings a job's host coefficients in, the
@@ -92,7 +93,7 @@ struct pc_group_srs {
 
 namespace {
 
-size_t fq_bytes(pc_curve c) { return c == PC_CURVE_BLS12_381 ? 48 : 32; }
+size_t fq_bytes(pc_curve c) { return pc_fq_bytes(c); }
 
 // run fn(d) for every device on that device's worker thread and wait for all of them; returns the first non-OK status
 template <class Fn>
@@ -194,7 +195,7 @@ pc_ctx* pc_hip_group_ctx(pc_group* g, int i) { return (g && i >= 0 && (size_t)i 
 
 int pc_hip_group_srs_upload(pc_group* g, pc_curve curve, const void* bases_host, size_t n, size_t stride_bytes, int precompute,
                             pc_group_srs** out) {
-  if (!g || !out || (!bases_host && n) || (int)curve < 0 || (int)curve > 2) return PC_ERR_INVALID_ARG;
+  if (!g || !out || (!bases_host && n) || !pc_known_curve(curve)) return PC_ERR_INVALID_ARG;
   *out = nullptr;
   const size_t pb = 2 * fq_bytes(curve);
   if (stride_bytes == 0) stride_bytes = pb;
@@ -295,6 +296,7 @@ int pc_hip_group_kzg_open(pc_group* g, const pc_group_srs* s, const void* coeffs
     switch (s->curve) {
       case PC_CURVE_BLS12_381: rc = open_carries<pc_bls12_381_fr>(evals, len, z_host, carry, (uint64_t*)out_value_host); break;
       case PC_CURVE_BN254: rc = open_carries<pc_bn254_fr>(evals, len, z_host, carry, (uint64_t*)out_value_host); break;
+      case PC_CURVE_BLS12_377: rc = open_carries<pc_bls12_377_fr>(evals, len, z_host, carry, (uint64_t*)out_value_host); break;
       default: rc = open_carries<pc_pallas_fr>(evals, len, z_host, carry, (uint64_t*)out_value_host); break;
     }
   }
@@ -427,6 +429,7 @@ void job_phase_a(pc_group_job* j, size_t d, int r) {
     switch (s->curve) {
       case PC_CURVE_BLS12_381: rc = open_carries<pc_bls12_381_fr>(j->evals, j->len, j->z, j->carry, (uint64_t*)j->out_value); break;
       case PC_CURVE_BN254: rc = open_carries<pc_bn254_fr>(j->evals, j->len, j->z, j->carry, (uint64_t*)j->out_value); break;
+      case PC_CURVE_BLS12_377: rc = open_carries<pc_bls12_377_fr>(j->evals, j->len, j->z, j->carry, (uint64_t*)j->out_value); break;
       default: rc = open_carries<pc_pallas_fr>(j->evals, j->len, j->z, j->carry, (uint64_t*)j->out_value); break;
     }
   }

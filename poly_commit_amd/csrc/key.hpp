@@ -88,7 +88,7 @@ struct pc_job {
   bool done = false; int status = 0;
 };
 
-inline int fq_bytes(pc_curve c) { return c == PC_CURVE_BLS12_381 ? 48 : 32; }
+inline int fq_bytes(pc_curve c) { return (int)pc_fq_bytes(c); }
 // the affine encoding of the point at infinity: all words zero
 inline bool affine_is_zero(const uint32_t* xy, int aw) { uint32_t acc = 0; for (int i = 0; i < aw; i++) acc |= xy[i]; return acc == 0; }
 // windows of the key's table: the 255-bit scalar's, or those of its 130-bit GLV halves

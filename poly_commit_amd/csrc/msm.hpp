@@ -303,6 +303,7 @@ PC_HD void partial_slot_range(const uint32_t* offs, uint32_t key, uint32_t T, ui
 // 4. accumulate: one chunk of T sorted entries per lane
 // ---------------------------------------------------------------------------------------
 // the form of the running sum: radix 2^30 for BLS12-381 (ec.hpp XyzzR30; PC_ACC_R30, fp30.hpp), the 12- / 8-limb XyzzD otherwise
+// (BLS12-377 included: fp30.hpp is written against BLS12-381's modulus)
 template <class C> struct AccSum { static constexpr bool R30 = false; typedef XyzzD<C> type; };
 #if PC_ACC_R30
 template <> struct AccSum<pc_curve_bls12_381> { static constexpr bool R30 = true; typedef XyzzR30 type; };

@@ -20,7 +20,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdexcept>
 #include "../../include/pc_hip.h"
+#include "curves.hpp"
 #include "hip_backend.hpp"
 #include "msm.hpp"
 #include "sprs.hpp"
@@ -112,14 +114,27 @@ struct FieldOps {
 
 // (accessor functions rather than global tables: a namespace-scope constant would also be emitted into the
 // device image, where the host function addresses do not exist)
-const CurveOps& curve_ops_bls12_381(); const CurveOps& curve_ops_bn254(); const CurveOps& curve_ops_pallas();
-const FieldOps& field_ops_bls12_381(); const FieldOps& field_ops_bn254(); const FieldOps& field_ops_pallas();
+const CurveOps& curve_ops_bls12_381(); const CurveOps& curve_ops_bn254(); const CurveOps& curve_ops_pallas(); const CurveOps& curve_ops_bls12_377();
+const FieldOps& field_ops_bls12_381(); const FieldOps& field_ops_bn254(); const FieldOps& field_ops_pallas(); const FieldOps& field_ops_bls12_377();
 
+// (the entry points have refused every id outside [0, PC_CURVE_LAST], curves.hpp, before they come here)
 inline const CurveOps& curve_ops(pc_curve c) {
-  return c == PC_CURVE_BLS12_381 ? curve_ops_bls12_381() : c == PC_CURVE_BN254 ? curve_ops_bn254() : curve_ops_pallas();
+  switch (c) {
+    case PC_CURVE_BLS12_381: return curve_ops_bls12_381();
+    case PC_CURVE_BN254: return curve_ops_bn254();
+    case PC_CURVE_PALLAS: return curve_ops_pallas();
+    case PC_CURVE_BLS12_377: return curve_ops_bls12_377();
+  }
+  throw std::invalid_argument("unknown curve id");
 }
 inline const FieldOps& field_ops(pc_curve c) {
-  return c == PC_CURVE_BLS12_381 ? field_ops_bls12_381() : c == PC_CURVE_BN254 ? field_ops_bn254() : field_ops_pallas();
+  switch (c) {
+    case PC_CURVE_BLS12_381: return field_ops_bls12_381();
+    case PC_CURVE_BN254: return field_ops_bn254();
+    case PC_CURVE_PALLAS: return field_ops_pallas();
+    case PC_CURVE_BLS12_377: return field_ops_bls12_377();
+  }
+  throw std::invalid_argument("unknown curve id");
 }
 
 // hash-only kernels (hash_tu.hip)

@@ -5,7 +5,7 @@
 // (ipa_pc/data_structures.rs:17-36): this decoder is what lets a prover load a ceremony file / a stored key straight
 // into HBM.  The point encodings live in ark-ec / ark-serialize / ark-bls12-381 0.5 (not under /root/reference) and are
 // restated from their published behaviour -- the same statement as host/transcript.hpp:
-//   generic short Weierstrass (BN254 G1, Pallas)
+//   generic short Weierstrass (BN254 G1, Pallas, BLS12-377 G1)
 //     uncompressed  x: ceil(bits/8) bytes LE, y: ceil((bits+2)/8) bytes LE, flags in the top bits of the LAST byte
 //     compressed    x: ceil((bits+2)/8) bytes LE with the flags in the top bits of the last byte
 //     flags         0x80 YIsNegative (y > -y: the larger of the two roots; no bit = YIsPositive = the smaller), 0x40 PointAtInfinity
@@ -13,7 +13,8 @@
 //     uncompressed  x, y: 48 bytes big-endian each; byte 0: 0x80 clear, 0x40 infinity
 //     compressed    x: 48 bytes big-endian; byte 0: 0x80 set, 0x40 infinity, 0x20 y is the lexicographically larger root
 // Compressed points need a square root: y = (x^3 + b)^((p+1)/4) for p = 3 (mod 4) (BLS12-381, BN254); Tonelli-Shanks with
-// the field's 2^s-th root of unity for Pallas (p = 1 mod 2^32): ~255 + up to s^2/2 squarings per point, once per key.
+// the field's 2^s-th root of unity for Pallas (p = 1 mod 2^32) and BLS12-377 (p = 1 mod 2^46): ~bits + up to s^2/2 squarings per point,
+// once per key.
 // SrsEncodeBody is the inverse (resident points -> ark-serialize bytes): what CanonicalSerialize writes for a Vec<G1Affine>.
 #pragma once
 #include "ec.hpp"

@@ -18,7 +18,8 @@
 //
 // Field addition is exact, so the order of summation is free: products are taken in pairs with one Montgomery reduction per pair
 // (mul_add_mul) and every stored element is a canonical residue (the column hash absorbs the bytes).  The lazy (_lz) forms of fp32.hpp
-// need spare top bits that none of the three scalar fields has (R >= 8p for the fused pair: none; 4p within the limbs: BN254 Fr only).  Each output has one owner: no
+// need spare top bits that none of the three scalar fields it was built for has (R >= 8p for the fused pair: none; 4p within the limbs: BN254 Fr only;
+// BLS12-377's 253-bit Fr has both and runs the same canonical forms).  Each output has one owner: no
 // atomics.  Everything is PC_HD and templated on the backend, so tests/emu steps the same bodies lane by lane on the CPU.
 #pragma once
 #include <stddef.h>

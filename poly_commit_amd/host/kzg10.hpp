@@ -27,6 +27,7 @@ namespace pc_host {
 struct Bls12_381 { typedef pc_curve_bls12_381 C; static constexpr pc_curve ID = PC_CURVE_BLS12_381; static constexpr int NQ = 6; };
 struct Bn254 { typedef pc_curve_bn254 C; static constexpr pc_curve ID = PC_CURVE_BN254; static constexpr int NQ = 4; };
 struct Pallas { typedef pc_curve_pallas C; static constexpr pc_curve ID = PC_CURVE_PALLAS; static constexpr int NQ = 4; };
+struct Bls12_377 { typedef pc_curve_bls12_377 C; static constexpr pc_curve ID = PC_CURVE_BLS12_377; static constexpr int NQ = 6; };
 
 // Error variants of poly-commit/src/error.rs that this path can raise.
 struct Error {

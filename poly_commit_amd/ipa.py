@@ -19,6 +19,7 @@ FQ_MODULUS = {
     "bls12_381": 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab,
     "bn254": 21888242871839275222246405745257275088696311157297823662689037894645226208583,
     "pallas": 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
+    "bls12_377": 0x1ae3a4617c510eac63b05c06ca1493b1a22d9f300f5138f1ef3622fba094800170b5d44300000008508c00000000001,
 }
 
 

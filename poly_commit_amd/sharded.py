@@ -24,6 +24,7 @@ FR_MODULUS = {
     "bls12_381": 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001,
     "bn254": 21888242871839275222246405745257275088548364400416034343698204186575808495617,
     "pallas": 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001,
+    "bls12_377": 0x12ab655e9a2ca55660b44d1e5c37b00159aa76fed00000010a11800000000001,
 }
 _R = 1 << 256
 

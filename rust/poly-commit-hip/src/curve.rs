@@ -34,7 +34,7 @@ pub trait HipField: PrimeField {
 /// A G1 / Pedersen group in short-Weierstrass affine form that the library has kernels for.
 pub trait HipCurve: AffineRepr {
     const CURVE: c_int;
-    /// 64-bit limbs of one base-field element (6 for BLS12-381, 4 for BN254 / Pallas).
+    /// 64-bit limbs of one base-field element (6 for BLS12-381 / BLS12-377, 4 for BN254 / Pallas).
     const FQ_LIMBS: usize;
     /// x || y in Montgomery limbs; the point at infinity is (0, 0) in the packed form.
     fn write_xy(&self, out: &mut [u64]);
@@ -63,6 +63,7 @@ macro_rules! impl_hip_field {
 impl_hip_field!(ark_bls12_381::Fr, ffi::PC_CURVE_BLS12_381);
 impl_hip_field!(ark_bn254::Fr, ffi::PC_CURVE_BN254);
 impl_hip_field!(ark_pallas::Fr, ffi::PC_CURVE_PALLAS);
+impl_hip_field!(ark_bls12_377::Fr, ffi::PC_CURVE_BLS12_377);
 
 macro_rules! impl_hip_curve {
     ($cfg:ty, $fq:ty, $n:expr, $id:expr) => {
@@ -109,6 +110,7 @@ macro_rules! impl_hip_curve {
 impl_hip_curve!(ark_bls12_381::g1::Config, ark_bls12_381::Fq, 6, ffi::PC_CURVE_BLS12_381);
 impl_hip_curve!(ark_bn254::g1::Config, ark_bn254::Fq, 4, ffi::PC_CURVE_BN254);
 impl_hip_curve!(ark_pallas::PallasConfig, ark_pallas::Fq, 4, ffi::PC_CURVE_PALLAS);
+impl_hip_curve!(ark_bls12_377::g1::Config, ark_bls12_377::Fq, 6, ffi::PC_CURVE_BLS12_377);
 
 /// Packed `n x (x || y)` limbs of a slice of points (the ABI's 96 / 64-byte form).
 pub fn pack_points<G: HipCurve>(pts: &[G]) -> Vec<u64> {

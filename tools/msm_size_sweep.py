@@ -14,10 +14,30 @@ if os.environ.get("PC_SWEEP_CHUNK"): ctx.set_msm_tuning(0, int(os.environ["PC_SW
 out = {}
 curves = os.environ.get("PC_SWEEP_CURVES", "bls12_381").split(",")
 sizes = [int(x) for x in os.environ.get("PC_SWEEP_LOGS", "8,10,12,14,16,18,20").split(",")]
+def device_made_inputs(curve, nmax):
+    """A curve the CPU oracle does not have (BLS12-377): the bases are k_i G for seeded random k_i, made on the device by
+    pc_hip_fixed_base_batch_mul; the scalars are seeded random residues below 2^252 < r, taken as Montgomery forms."""
+    from harness import ref377 as B
+    assert curve == B.CURVE
+    rng = np.random.default_rng(3)
+    def residues():
+        a = rng.integers(0, 1 << 63, size=(nmax, 4), dtype=np.int64)
+        a[:, 3] &= (1 << 60) - 1
+        return torch.from_numpy(a).cuda()
+    ks = residues()
+    pts = torch.empty((nmax, 12), dtype=torch.int64, device="cuda")
+    ctx.fixed_base_batch_mul(curve, B.point(B.G), ks.data_ptr(), nmax, pts.data_ptr())
+    torch.cuda.synchronize()
+    return pts.data_ptr(), residues(), pts
+
+
 for curve in curves:
     nmax = 1 << max(sizes)
-    bases = O.gen_bases(curve, nmax)
-    sc = torch.from_numpy(O.f_to_mont(curve, 1, O.gen_scalars(curve, 3, nmax)).view(np.int64)).cuda()
+    if curve in O.pyref.CURVES:
+        bases = O.gen_bases(curve, nmax)
+        sc = torch.from_numpy(O.f_to_mont(curve, 1, O.gen_scalars(curve, 3, nmax)).view(np.int64)).cuda()
+    else:
+        bases, sc, keep = device_made_inputs(curve, nmax)
     torch.cuda.synchronize()
     row = {}
     for lg in sizes:
