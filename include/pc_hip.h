@@ -563,6 +563,58 @@ int pc_hip_ml_setup(pc_ctx* ctx, pc_curve curve, unsigned nv, const void* g_xy_h
 int pc_hip_ml_trim(pc_ctx* ctx, const pc_srs* powers_of_g, const pc_g2_srs* powers_of_h, unsigned nv, unsigned supported,
                    pc_srs** out_powers_of_g0, pc_g2_srs** out_pair_key);
 
+/* ---- streaming_kzg: multi-point openings and the folds of Gemini's tensor check (poly-commit/src/streaming_kzg) -------------
+ * The reference streams coefficients highest degree first against a reversed key; here every array is in natural order (index =
+ * degree, Fr in Montgomery form) and the key is a resident pc_srs whose point base_offset + d is tau^d G.  Both of the reference's
+ * implementations (time.rs on resident vectors, space.rs on streams) return the same commitments and proofs (tests.rs:40-83); these
+ * entry points compute that common definition.  They take every pc_curve (no pairing is involved).  Host inputs are copied whole.
+ *   folding tree: f_0 = f (n >= 1 coefficients), L_i = ceil(n / 2^i), f_i[b] = f_{i-1}[2b] + rho_{i-1} f_{i-1}[2b + 1] for
+ *     b < L_i, a coefficient past the end of f_{i-1} being zero (FoldedPolynomialTree, data_structures.rs:12-138: init_stack pads the
+ *     high end); depth > log2 n repeats the single coefficient.
+ *   division: Z(x) = prod_{j<k} (x - z_j) (repeated points allowed), q = p div Z with max(n - k, 0) coefficients, r = p mod Z as k
+ *     coefficients HIGHEST DEGREE FIRST (r[0] multiplies x^(k-1): state.make_contiguous(), space.rs:133); n < k: q empty, r = p
+ *     zero-extended at the high end.
+ * Checks made before the device is touched: a null pointer, n, depth, k or count of 0, a key of another context or one shorter than
+ * the longest vector multiplied past base_offset, and an unknown curve id are PC_ERR_INVALID_ARG; k > PC_HIP_MAX_EVAL_POINTS,
+ * depth > PC_HIP_MAX_FOLD_DEPTH and n >= 2^32 are PC_ERR_TOO_LARGE.  The key is never modified; scratch is the context's grow-only
+ * staging (pc_hip_ctx_trim releases it) or, above 1 GiB, freed when the call returns. */
+#define PC_HIP_MAX_EVAL_POINTS 16
+#define PC_HIP_MAX_FOLD_DEPTH 64
+/* FoldedPolynomialTree::iterator (data_structures.rs:64-138), all levels at once: level i (1 .. depth) is written to out_dev at the
+ * element offset level_offsets_host[i - 1] = L_1 + .. + L_{i-1} (an output, `depth` entries); out_capacity_elems < sum L_i is
+ * PC_ERR_INVALID_ARG.  coeffs: host or device; challenges_host: depth Fr. */
+int pc_hip_fold_tree(pc_ctx* ctx, pc_curve field_of, const void* coeffs, pc_mem where_in, size_t n, const void* challenges_host,
+                     size_t depth, void* out_dev, size_t out_capacity_elems, size_t* level_offsets_host);
+/* The division of CommitterKeyStream::open_multi_points (space.rs:110-133) and of CommitterKey::open_multi_points (time.rs:126-137:
+ * `p / vanishing_polynomial(eval_points)`) without the MSM: quotient_out (max(n - k, 0) Fr, host or device, may be NULL) and
+ * remainder_host (k Fr, highest degree first). */
+int pc_hip_poly_div_multi(pc_ctx* ctx, pc_curve field_of, const void* coeffs, pc_mem where_in, size_t n, const void* points_host,
+                          size_t k, void* quotient_out, pc_mem where_out, void* remainder_host);
+/* CommitterKeyStream::open_multi_points (space.rs:98-136) / CommitterKey::open_multi_points (time.rs:126-137) as one call:
+ * out = sum_d q[d] * bases[base_offset + d], q = p div Z; remainder_host (k Fr, highest degree first) may be NULL.  n < k is
+ * PC_ERR_INVALID_ARG (space.rs asserts it; the time form's identity for n <= k is host/streaming_kzg.hpp's); n = k gives infinity. */
+int pc_hip_kzg_open_multi(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, const void* coeffs, pc_mem where, size_t n,
+                          const void* points_host, size_t k, void* remainder_host, void* out_xy, int* out_is_infinity);
+/* CommitterKey::batch_open_multi_points (time.rs:141-152): pc_hip_kzg_open_multi of sum_j eta^j polys[j] (linear_combination and
+ * powers, mod.rs:288-310; shorter polynomials are zero-extended).  polys: count pointers, all host or all device; lens: their
+ * lengths; eta_host: one Fr.  The longest polynomial having at most k coefficients gives infinity (time.rs:134-136). */
+int pc_hip_kzg_batch_open_multi(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, const void* const* polys, pc_mem where,
+                                const size_t* lens, size_t count, const void* points_host, size_t k, const void* eta_host,
+                                void* out_xy, int* out_is_infinity);
+/* CommitterKeyStream::commit_folding (space.rs:165-205): out_xy[i - 1] = sum_{b < L_i} f_i[b] * bases[base_offset + b] for
+ * i = 1 .. depth; out_is_infinity: depth flags, or NULL.  The tree is made on the device and never leaves it. */
+int pc_hip_kzg_commit_folding(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, const void* coeffs, pc_mem where, size_t n,
+                              const void* challenges_host, size_t depth, void* out_xy, int* out_is_infinity);
+/* CommitterKeyStream::open_folding (space.rs:209-262): remainders_host[(i - 1) k ..] = f_i mod Z for i = 1 .. depth (level 0 is not
+ * opened, :239-242), out = sum_d s[d] * bases[base_offset + d] with s[d] = sum_i etas[i - 1] * (f_i div Z)[d], d < L_1 - k; infinity
+ * if L_1 <= k.  A level with L_i <= k has an empty quotient and r_i = f_i zero-extended.  etas_host: depth Fr. */
+int pc_hip_kzg_open_folding(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, const void* coeffs, pc_mem where, size_t n,
+                            const void* challenges_host, size_t depth, const void* points_host, size_t k, const void* etas_host,
+                            void* remainders_host, void* out_xy, int* out_is_infinity);
+/* Kernel launches of the last call of this family on the context's own queue: [folding tree, divisions and combination] (the MSMs'
+ * launches are their pipelines').  A measurement hook (tools/skzg_timing.py). */
+int pc_hip_last_skzg_launches(const pc_ctx* ctx, unsigned out[2]);
+
 /* ---- One committer key over several GPUs of a node, driven from one process ----------------
  * The reference has no multi-device path; this is the form a prover that holds ONE CommitterKey needs.  The key is
  * cut into N contiguous chunks, one per device (chunk d also keeps the one power below it, so that commit and open

@@ -158,6 +158,13 @@ def load_library():
     lib.pc_hip_g2_srs_device_ptr.restype = vp
     lib.pc_hip_ml_setup.argtypes = [vp, ip, C.c_uint, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
     lib.pc_hip_ml_trim.argtypes = [vp, vp, vp, C.c_uint, C.c_uint, C.POINTER(vp), C.POINTER(vp)]
+    lib.pc_hip_fold_tree.argtypes = [vp, ip, vp, ip, sz, vp, sz, vp, sz, C.POINTER(sz)]
+    lib.pc_hip_poly_div_multi.argtypes = [vp, ip, vp, ip, sz, vp, sz, vp, ip, vp]
+    lib.pc_hip_kzg_open_multi.argtypes = [vp, vp, sz, vp, ip, sz, vp, sz, vp, vp, C.POINTER(C.c_int)]
+    lib.pc_hip_kzg_batch_open_multi.argtypes = [vp, vp, sz, C.POINTER(vp), ip, C.POINTER(sz), sz, vp, sz, vp, vp, C.POINTER(C.c_int)]
+    lib.pc_hip_kzg_commit_folding.argtypes = [vp, vp, sz, vp, ip, sz, vp, sz, vp, C.POINTER(C.c_int)]
+    lib.pc_hip_kzg_open_folding.argtypes = [vp, vp, sz, vp, ip, sz, vp, sz, vp, sz, vp, vp, vp, C.POINTER(C.c_int)]
+    lib.pc_hip_last_skzg_launches.argtypes = [vp, C.POINTER(C.c_uint)]
     _lib = lib
     return lib
 
@@ -386,6 +393,39 @@ class Context:
                                                  pout, wout))
         return out
 
+    # ---- streaming_kzg: the folding tree and the division by a vanishing polynomial ------------------
+    def fold_tree(self, curve, coeffs, challenges, out_dev, out_capacity, n=None):
+        """pc_hip_fold_tree: every level f_1 .. f_depth of the folding tree of `coeffs` ((n, 4) uint64 host array or a device pointer
+        with n) into the device buffer out_dev; challenges: (depth, 4).  Returns the element offsets of the levels."""
+        pin, win = _ptr(coeffs)
+        if n is None:
+            n = coeffs.shape[0]
+        ch = np.ascontiguousarray(challenges, dtype=np.uint64)
+        depth = ch.shape[0]
+        offs = (C.c_size_t * max(depth, 1))()
+        self.check(self.lib.pc_hip_fold_tree(self.h, CURVES[curve], pin, win, n, C.c_void_p(ch.ctypes.data), depth, C.c_void_p(out_dev), out_capacity, offs))
+        return list(offs)[:depth]
+
+    def poly_div_multi(self, curve, coeffs, points, n=None, want_quotient=True):
+        """pc_hip_poly_div_multi: (q, r) = (p div Z, p mod Z), Z = prod (x - points[j]); r: (k, 4), highest degree first; q: (max(n - k,
+        0), 4) on the host, or None."""
+        pin, win = _ptr(coeffs)
+        if n is None:
+            n = coeffs.shape[0]
+        z = np.ascontiguousarray(points, dtype=np.uint64)
+        k = z.shape[0]
+        q = np.zeros((max(n - k, 0), 4), dtype=np.uint64) if want_quotient else None
+        r = np.zeros((k, 4), dtype=np.uint64)
+        self.check(self.lib.pc_hip_poly_div_multi(self.h, CURVES[curve], pin, win, n, C.c_void_p(z.ctypes.data), k,
+                                                  C.c_void_p(q.ctypes.data) if want_quotient and q.size else None, PC_MEM_HOST, C.c_void_p(r.ctypes.data)))
+        return q, r
+
+    def last_skzg_launches(self):
+        """kernel launches of the last streaming_kzg call: (folding tree, divisions + combination)"""
+        out = (C.c_uint * 2)()
+        self.check(self.lib.pc_hip_last_skzg_launches(self.h, out))
+        return int(out[0]), int(out[1])
+
     # ---- IPA round primitives (device-resident vectors; `dev` = raw device pointer) --------------
     def fr_fold(self, curve, lo_dev, hi_dev, n_half, s):
         s = np.ascontiguousarray(s, dtype=np.uint64)
@@ -600,6 +640,71 @@ class Srs:
         self.ctx.check(self.ctx.lib.pc_hip_kzg_open(self.ctx.h, self.h, base_offset, p, where, n, C.c_void_p(z.ctypes.data),
                                                     C.c_void_p(out.ctypes.data), C.byref(inf)))
         return out, bool(inf.value)
+
+    def _point_out(self):
+        return np.zeros(2 * FQ_BYTES[self.curve] // 8, dtype=np.uint64), C.c_int(0)
+
+    def kzg_open_multi(self, coeffs, points, n=None, base_offset=0):
+        """open_multi_points of streaming_kzg as one call (pc_hip_kzg_open_multi): one proof for p at all `points` ((k, 4) uint64).
+        Returns (xy, is_infinity, remainder (k, 4) highest degree first)."""
+        p, where = _ptr(coeffs)
+        if n is None:
+            n = coeffs.shape[0]
+        z = np.ascontiguousarray(points, dtype=np.uint64)
+        r = np.zeros((z.shape[0], 4), dtype=np.uint64)
+        out, inf = self._point_out()
+        self.ctx.check(self.ctx.lib.pc_hip_kzg_open_multi(self.ctx.h, self.h, base_offset, p, where, n, C.c_void_p(z.ctypes.data), z.shape[0],
+                                                          C.c_void_p(r.ctypes.data), C.c_void_p(out.ctypes.data), C.byref(inf)))
+        return out, bool(inf.value), r
+
+    def kzg_batch_open_multi(self, polys, points, eta, lens=None, base_offset=0):
+        """batch_open_multi_points (pc_hip_kzg_batch_open_multi): the proof of sum_j eta^j polys[j] at all `points`.  polys: host arrays,
+        or device pointers with `lens`.  Returns (xy, is_infinity)."""
+        ptrs = [_ptr(p) for p in polys]
+        where = ptrs[0][1]
+        assert all(w == where for _, w in ptrs)
+        if lens is None:
+            lens = [p.shape[0] for p in polys]
+        arr = (C.c_void_p * len(polys))(*[p for p, _ in ptrs])
+        larr = (C.c_size_t * len(polys))(*lens)
+        z = np.ascontiguousarray(points, dtype=np.uint64)
+        eta = np.ascontiguousarray(eta, dtype=np.uint64)
+        out, inf = self._point_out()
+        self.ctx.check(self.ctx.lib.pc_hip_kzg_batch_open_multi(self.ctx.h, self.h, base_offset, arr, where, larr, len(polys), C.c_void_p(z.ctypes.data),
+                                                                z.shape[0], C.c_void_p(eta.ctypes.data), C.c_void_p(out.ctypes.data), C.byref(inf)))
+        return out, bool(inf.value)
+
+    def kzg_commit_folding(self, coeffs, challenges, n=None, base_offset=0):
+        """commit_folding (pc_hip_kzg_commit_folding): the commitments of the levels f_1 .. f_depth of the folding tree.
+        Returns ((depth, 2*Fq limbs) points, (depth,) infinity flags)."""
+        p, where = _ptr(coeffs)
+        if n is None:
+            n = coeffs.shape[0]
+        ch = np.ascontiguousarray(challenges, dtype=np.uint64)
+        depth = ch.shape[0]
+        out = np.zeros((depth, 2 * FQ_BYTES[self.curve] // 8), dtype=np.uint64)
+        inf = (C.c_int * max(depth, 1))()
+        self.ctx.check(self.ctx.lib.pc_hip_kzg_commit_folding(self.ctx.h, self.h, base_offset, p, where, n, C.c_void_p(ch.ctypes.data), depth,
+                                                              C.c_void_p(out.ctypes.data), inf))
+        return out, np.array(list(inf)[:depth], dtype=bool)
+
+    def kzg_open_folding(self, coeffs, challenges, points, etas, n=None, base_offset=0):
+        """open_folding (pc_hip_kzg_open_folding): every level's remainder modulo Z and the one proof over the eta-combined quotients.
+        Returns (remainders (depth, k, 4) highest degree first, xy, is_infinity)."""
+        p, where = _ptr(coeffs)
+        if n is None:
+            n = coeffs.shape[0]
+        ch = np.ascontiguousarray(challenges, dtype=np.uint64)
+        z = np.ascontiguousarray(points, dtype=np.uint64)
+        et = np.ascontiguousarray(etas, dtype=np.uint64)
+        depth, k = ch.shape[0], z.shape[0]
+        assert et.shape[0] == depth
+        rem = np.zeros((depth, k, 4), dtype=np.uint64)
+        out, inf = self._point_out()
+        self.ctx.check(self.ctx.lib.pc_hip_kzg_open_folding(self.ctx.h, self.h, base_offset, p, where, n, C.c_void_p(ch.ctypes.data), depth,
+                                                            C.c_void_p(z.ctypes.data), k, C.c_void_p(et.ctypes.data), C.c_void_p(rem.ctypes.data),
+                                                            C.c_void_p(out.ctypes.data), C.byref(inf)))
+        return rem, out, bool(inf.value)
 
     def msm_many(self, scalars, m=None, n_msms=None, base_offset=0, montgomery=False):
         """n_msms MSMs of m pairs over bases[base_offset : base_offset + m] (pc_hip_msm_many; Hyrax's

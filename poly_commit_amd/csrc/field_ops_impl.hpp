@@ -8,6 +8,7 @@
 #include "ipa.hpp"
 #include "hash.hpp"
 #include "sprs.hpp"
+#include "skzg.hpp"
 
 namespace pc {
 
@@ -101,9 +102,16 @@ struct FieldOpsImpl {
   static void brakedown_encode_f(HipBackend& be, const BrakedownDev& code, const uint32_t* msgs, uint32_t rows, uint32_t* T, uint32_t* out) {
     brakedown_encode<FrP>(be, code, msgs, rows, T, out);
   }
+  static_assert(SKZG_TILE == SKZG_TILE_ELEMS && sizeof(SkzgDivDesc) == 24 && FrP::N == 8, "pc_internal.hpp sizes the division's scratch");
+  static uint32_t fold_tree_f(HipBackend& be, const uint32_t* f, size_t n, const uint32_t* rho, uint32_t depth, uint32_t* out, const uint64_t* offs) {
+    return fold_tree<FrP>(be, f, n, rho, depth, out, offs);
+  }
+  static uint32_t div_multi_f(HipBackend& be, const SkzgDivLevel* lv, size_t count, const uint32_t* z, uint32_t k, uint32_t* rem, void* scratch, uint32_t fan) {
+    return div_multi<FrP>(be, lv, count, z, k, rem, scratch, fan);
+  }
   static FieldOps table() {
     return FieldOps{&make_ntt, &poly_eval_f, &div_scan_f, &witness_f, &fr_fold, &fr_dot, &ipa_fold_dots, &fr_powers, &ipa_key_scalars, &fr_lincomb, &column_hash,
-                    &column_hash_part, &brakedown_encode_f, &brakedown_points<FrP>};
+                    &column_hash_part, &brakedown_encode_f, &brakedown_points<FrP>, &fold_tree_f, &div_multi_f};
   }
 };
 

@@ -48,6 +48,7 @@ struct pc_ctx {
   std::vector<struct pc_g2_srs*> g2_keys;   // every G2 key object of this context that is alive (the functions at the end of this header own them)
   std::vector<struct pc_lincode*> codes;   // every Brakedown code object of this context that is alive; abi_lincode.hip alone creates and releases them
   float brakedown_phases[4] = {0, 0, 0, 0};
+  uint32_t skzg_launches[2] = {0, 0};      // kernel launches of the last streaming_kzg call: [folding tree, divisions + combination] (pc_hip_last_skzg_launches)
 };
 
 // What a key of either group is: n affine points resident on the device, registered in its context

@@ -2,7 +2,8 @@
 //
 // The library is built from several .hip files compiled in parallel (poly_commit_amd/build.py):
 //   abi_<subject>.hip  the extern "C" entry points (include/pc_hip.h), one unit per subject: ctx (context, errors, memory, timing),
-//                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa, lincode (the Brakedown code object); staging,
+//                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa, lincode (the Brakedown code object),
+//                      skzg (streaming_kzg: folding tree, multi-point openings); staging,
 //                      error translation
 //   key.hpp            host only: the key objects -- pc_key_base and what G1 and G2 keys share over it (fill, read-back, registry,
 //                      locked free), pc_srs with its pipelines and the derived keys of an opening, pc_g2_srs -- their whole lifetime
@@ -14,7 +15,7 @@
 //   host_tail.hpp      host only: 64-bit-limb points of either group -- the MSM's Horner tail, affine -> XYZZ, one scalar
 //                      multiplication, a sum of points, the fixed base's window table
 //   field_<name>.hip   everything templated on one scalar field: NTT, division scan, IPA vector kernels,
-//                      column digests, the Brakedown encoder (sprs.hpp)
+//                      column digests, the Brakedown encoder (sprs.hpp), the folding tree and multi-point division (skzg.hpp)
 // The abi units reach the templates through the two tables of plain function pointers below, one
 // instance per curve / field.
 #pragma once
@@ -90,6 +91,14 @@ struct CurveOps {
   void (*fr_one)(uint32_t* out_mont);
 };
 
+// streaming_kzg: coefficients of one tile (skzg.hpp: what one workgroup folds or divides in LDS), one polynomial of a division
+// (q: max(len - k, 0) coefficients; longer than a tile: the element in front of q is written too), the division's scratch
+constexpr uint32_t SKZG_TILE = 1024;
+struct SkzgDivLevel { const uint32_t* src; uint32_t len; uint32_t* q; };
+inline size_t skzg_div_scratch_bytes(size_t max_len, size_t count, uint32_t k) {
+  return (2 * (max_len > SKZG_TILE ? max_len : 0) + count * k + k) * 32 + count * 24 + 64;
+}
+
 struct FieldOps {
   NttRunner* (*make_ntt)(HipBackend& be, unsigned log_n);
   void (*poly_eval)(HipBackend& be, const uint32_t* x, size_t n, const uint32_t* z_host, uint32_t* out_host, uint32_t fan);
@@ -110,6 +119,11 @@ struct FieldOps {
   // one Brakedown encode of `rows` messages (sprs.hpp): row-major in and out, T = the transposed working buffer; two phase marks
   void (*brakedown_encode)(HipBackend& be, const BrakedownDev& code, const uint32_t* msgs, uint32_t rows, uint32_t* T, uint32_t* out);
   void (*brakedown_points)(uint32_t* out_host, size_t count);      // the base code's points 1, 2, .. in Montgomery form (host)
+  // streaming_kzg (skzg.hpp): every level of the folding tree into out at the element offsets offs_host; `count` polynomials divided by
+  // one vanishing polynomial, remainders on the host (highest degree first).  Both return their number of kernel launches.
+  uint32_t (*fold_tree)(HipBackend& be, const uint32_t* f, size_t n, const uint32_t* rho_host, uint32_t depth, uint32_t* out, const uint64_t* offs_host);
+  uint32_t (*div_multi)(HipBackend& be, const SkzgDivLevel* lv, size_t count, const uint32_t* z_host, uint32_t k, uint32_t* rem_host, void* scratch,
+                        uint32_t fan);
 };
 
 // (accessor functions rather than global tables: a namespace-scope constant would also be emitted into the
