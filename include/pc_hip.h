@@ -615,6 +615,67 @@ int pc_hip_kzg_open_folding(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, 
  * launches are their pipelines').  A measurement hook (tools/skzg_timing.py). */
 int pc_hip_last_skzg_launches(const pc_ctx* ctx, unsigned out[2]);
 
+/* ---- MarlinPST13: multivariate commit and open (poly-commit/src/marlin/marlin_pst13_pc) -----------------------------------
+ * A commitment and a proof are group elements, so they do not depend on the order of the key's BTreeMap (data_structures.rs:
+ * powers_of_g: BTreeMap<SparseTerm, G1Affine>); the device order is the following.  n = num_vars, d = the degree of the layout
+ * (max_degree of the universal parameters, supported_degree of a trimmed key), N(v, r) = C(v + r, v), M = N(n, d) monomials of
+ * total degree <= d, ordered lexicographically by (e_0 .. e_{n-1}), e_0 most significant:
+ *   rank(e) = sum_j [ N(n - j, r_j) - N(n - j, r_j - e_j) ],   r_j = d - (e_0 + .. + e_{j-1})
+ * The constant monomial is rank 0, X_{n-1}^d is rank d, X_0^d is rank M - 1; the monomials without X_0 .. X_{i-1} are exactly the
+ * prefix [0, N(n - i, d)), in the order of the layout (n - i, d).  A key is a resident pc_srs whose point base_offset + rank(e) is
+ * (prod_j beta_j^e_j) G; a polynomial is a dense vector of M Fr (Montgomery) in the same order, or T terms: `exps` (T x n bytes, the
+ * exponent of X_j of term t at exps[t n + j]) and `coeffs` (T Fr), both on the host or both on the device.  n = 1 is a univariate
+ * polynomial in natural order; its division runs on the scan of pc_hip_poly_div_scan.
+ * Limits, decided before the device is touched (PC_ERR_TOO_LARGE): n <= PC_HIP_PST13_MAX_VARS, d <= PC_HIP_PST13_MAX_DEGREE for
+ * n >= 2, M < 2^28; an entry point that takes or returns exponent tuples also needs d <= 255 for n = 1 (an exponent is one byte).
+ * A null pointer, n = 0, d = 0, an unknown curve id, a key of another context and a key shorter than base_offset + M are
+ * PC_ERR_INVALID_ARG.  They take every pc_curve (no pairing is involved); the key is never modified; scratch is the context's
+ * grow-only staging (pc_hip_ctx_trim releases it) or, above 1 GiB, freed when the call returns. */
+#define PC_HIP_PST13_MAX_VARS 32
+#define PC_HIP_PST13_MAX_DEGREE 255
+/* Layout helpers, host only, no context: how a shim sorts a BTreeMap key into device order.
+ * pc_hip_pst13_key_len: M, or 0 beyond the limits.  pc_hip_pst13_rank: out_ranks[t] = rank of the tuple exps[t n ..] (a tuple of
+ * degree > d is PC_ERR_INVALID_ARG).  pc_hip_pst13_unrank: the inverse (a rank >= M is PC_ERR_INVALID_ARG). */
+size_t pc_hip_pst13_key_len(size_t num_vars, size_t degree);
+int pc_hip_pst13_rank(size_t num_vars, size_t degree, const uint8_t* exps, size_t count, uint32_t* out_ranks);
+int pc_hip_pst13_unrank(size_t num_vars, size_t degree, const uint32_t* ranks, size_t count, uint8_t* out_exps);
+/* out_dev[rank(e)] = prod_j beta_j^e_j for all M ranks: `powers_of_beta` of setup (mod.rs:187-207) in device order, one lane per
+ * rank.  betas_host: n Fr.  pc_hip_fixed_base_batch_mul of the result is powers_of_g. */
+int pc_hip_pst13_monomial_evals(pc_ctx* ctx, pc_curve field_of, size_t num_vars, size_t degree, const void* betas_host, void* out_dev);
+/* Terms -> the dense vector out_dev (M Fr, zero where no term is): what SparsePolynomial::from_coefficients_vec does with a sort
+ * (the merge of like terms).  A repeated exponent tuple is PC_ERR_INVALID_ARG whatever its coefficients (the reference's
+ * SparsePolynomial never holds one), a term of degree > d as well (check_degrees_and_bounds, mod.rs:112-128, called at :342 and :437); zero
+ * coefficients and n_terms = 0 are allowed.  On an error out_dev is undefined. */
+int pc_hip_pst13_scatter(pc_ctx* ctx, pc_curve field_of, size_t num_vars, size_t degree, const void* exps, const void* coeffs, pc_mem where,
+                         size_t n_terms, void* out_dev);
+/* divide_at_point (mod.rs:44-92): p(X) - p(z) = sum_i (X_i - z_i) w_i(X), w_i without X_0 .. X_{i-1}.  Pass i divides the current
+ * polynomial along X_i, one lane per fiber (a tail e_{i+1} .. e_{n-1} with e_i running): w_i = (cur - cur|X_i = z_i) / (X_i - z_i) and
+ * cur = cur|X_i = z_i.  The reference drops the constants; here they stay, so the last remainder is p(z) (value_host, one Fr).
+ * poly: the dense vector (host or device), left unchanged; point_host: n Fr; quotients_dev: w_i as N(n - i, d) slots (its own dense
+ * vector in the layout (n - i, d)) at the element offset offsets_host[i] (an output, n entries: N(n, d) + .. + N(n - i + 1, d));
+ * capacity_elems < sum_i N(n - i, d) is PC_ERR_INVALID_ARG. */
+int pc_hip_pst13_divide(pc_ctx* ctx, pc_curve field_of, size_t num_vars, size_t degree, const void* poly, pc_mem where, const void* point_host,
+                        void* quotients_dev, size_t capacity_elems, size_t* offsets_host, void* value_host);
+/* MarlinPST13::commit without hiding (mod.rs:353-362: one msm_bigint over the key points of the polynomial's terms):
+ * out = sum_r p[r] * bases[base_offset + r], M pairs.  The polynomial is `dense` (where_dense), or, with dense == NULL, the n_terms
+ * terms exps / coeffs (where_terms), scattered first (pc_hip_pst13_scatter's errors). */
+int pc_hip_pst13_commit(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, size_t num_vars, size_t degree, const void* dense, pc_mem where_dense,
+                        const void* exps, const void* coeffs, pc_mem where_terms, size_t n_terms, void* out_xy, int* out_is_infinity);
+/* MarlinPST13::open without hiding (mod.rs:419-512: divide_at_point, then num_vars MSMs, :457-469): out_xy[i] = sum_r w_i[r] *
+ * bases[base_offset + r] over the prefix r < N(n - i, d) only -- no gather, no index list --, all n MSMs on the key's pipelines
+ * (pc_hip_msm_batch); value_host = p(z).  out_xy: n affine points; out_is_infinity: n flags, or NULL.  The polynomial as for
+ * pc_hip_pst13_commit.  The zero polynomial gives n infinities. */
+int pc_hip_pst13_open(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, size_t num_vars, size_t degree, const void* dense, pc_mem where_dense,
+                      const void* exps, const void* coeffs, pc_mem where_terms, size_t n_terms, const void* point_host, void* out_xy,
+                      int* out_is_infinity, void* value_host);
+/* MarlinPST13::trim's selection of powers_of_g (mod.rs:266-317: the terms of degree <= supported_degree), device to device:
+ * *out = a new resident key of N(n, supported_degree) points in the layout (n, supported_degree), out[rank_s(e)] = the point
+ * base_offset + rank_d(e) of srs.  supported_degree > degree is PC_ERR_INVALID_ARG (TrimmingDegreeTooLarge is the mirror's). */
+int pc_hip_pst13_trim(pc_ctx* ctx, const pc_srs* srs, size_t base_offset, size_t num_vars, size_t degree, size_t supported_degree, pc_srs** out);
+/* The last pc_hip_pst13_open of the context: out[0] = its number of MSMs, out[1] = 1 if it took the univariate route, out[2 + i] =
+ * the pairs given to MSM i.  A measurement hook (tests, tools/pst13_timing.py). */
+int pc_hip_last_pst13_shape(const pc_ctx* ctx, uint32_t out[34]);   /* 2 + PC_HIP_PST13_MAX_VARS words */
+
 /* ---- One committer key over several GPUs of a node, driven from one process ----------------
  * The reference has no multi-device path; this is the form a prover that holds ONE CommitterKey needs.  The key is
  * cut into N contiguous chunks, one per device (chunk d also keeps the one power below it, so that commit and open

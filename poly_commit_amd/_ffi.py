@@ -165,6 +165,17 @@ def load_library():
     lib.pc_hip_kzg_commit_folding.argtypes = [vp, vp, sz, vp, ip, sz, vp, sz, vp, C.POINTER(C.c_int)]
     lib.pc_hip_kzg_open_folding.argtypes = [vp, vp, sz, vp, ip, sz, vp, sz, vp, sz, vp, vp, vp, C.POINTER(C.c_int)]
     lib.pc_hip_last_skzg_launches.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.pc_hip_pst13_key_len.argtypes = [sz, sz]
+    lib.pc_hip_pst13_key_len.restype = sz
+    lib.pc_hip_pst13_rank.argtypes = [sz, sz, vp, sz, vp]
+    lib.pc_hip_pst13_unrank.argtypes = [sz, sz, vp, sz, vp]
+    lib.pc_hip_pst13_monomial_evals.argtypes = [vp, ip, sz, sz, vp, vp]
+    lib.pc_hip_pst13_scatter.argtypes = [vp, ip, sz, sz, vp, vp, ip, sz, vp]
+    lib.pc_hip_pst13_divide.argtypes = [vp, ip, sz, sz, vp, ip, vp, vp, sz, C.POINTER(sz), vp]
+    lib.pc_hip_pst13_commit.argtypes = [vp, vp, sz, sz, sz, vp, ip, vp, vp, ip, sz, vp, C.POINTER(C.c_int)]
+    lib.pc_hip_pst13_open.argtypes = [vp, vp, sz, sz, sz, vp, ip, vp, vp, ip, sz, vp, vp, C.POINTER(C.c_int), vp]
+    lib.pc_hip_pst13_trim.argtypes = [vp, vp, sz, sz, sz, sz, C.POINTER(vp)]
+    lib.pc_hip_last_pst13_shape.argtypes = [vp, C.POINTER(C.c_uint32)]
     _lib = lib
     return lib
 
@@ -184,6 +195,54 @@ def _ptr(x):
         assert x.is_contiguous()
         return C.c_void_p(x.data_ptr()), (PC_MEM_DEVICE if x.is_cuda else PC_MEM_HOST)
     raise TypeError(type(x))
+
+
+PST13_MAX_VARS = 32
+
+
+def pst13_key_len(num_vars, degree):
+    """M = C(num_vars + degree, num_vars), the length of a MarlinPST13 key in device order; 0 beyond the limits (pc_hip_pst13_key_len)"""
+    return int(load_library().pc_hip_pst13_key_len(num_vars, degree))
+
+
+def pst13_rank(num_vars, degree, exps):
+    """device-order ranks of exponent tuples: exps (count, num_vars) uint8 -> (count,) uint32 (pc_hip_pst13_rank)"""
+    lib = load_library()
+    e = np.ascontiguousarray(exps, dtype=np.uint8).reshape(-1, num_vars)
+    out = np.zeros(e.shape[0], dtype=np.uint32)
+    rc = lib.pc_hip_pst13_rank(num_vars, degree, C.c_void_p(e.ctypes.data), e.shape[0], C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise PcHipError(rc, lib.pc_hip_strerror(rc).decode())
+    return out
+
+
+def pst13_unrank(num_vars, degree, ranks):
+    """the inverse: ranks (count,) -> (count, num_vars) uint8 (pc_hip_pst13_unrank)"""
+    lib = load_library()
+    r = np.ascontiguousarray(ranks, dtype=np.uint32).reshape(-1)
+    out = np.zeros((r.shape[0], num_vars), dtype=np.uint8)
+    rc = lib.pc_hip_pst13_unrank(num_vars, degree, C.c_void_p(r.ctypes.data), r.shape[0], C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise PcHipError(rc, lib.pc_hip_strerror(rc).decode())
+    return out
+
+
+def _pst13_terms(num_vars, exps, coeffs, n_terms):
+    """(exps pointer, coeffs pointer, where, count, what must stay alive across the call) of a term list: host arrays ((T, n) uint8 and
+    (T, 4) uint64) or two device pointers with n_terms"""
+    if exps is None:
+        return None, None, PC_MEM_HOST, 0, None
+    if isinstance(exps, np.ndarray) or isinstance(exps, (list, tuple)):
+        e = np.ascontiguousarray(exps, dtype=np.uint8).reshape(-1, num_vars)
+        c = np.ascontiguousarray(coeffs, dtype=np.uint64).reshape(-1, 4)
+        assert e.shape[0] == c.shape[0]
+        if not e.shape[0]:
+            return None, None, PC_MEM_HOST, 0, None
+        return C.c_void_p(e.ctypes.data), C.c_void_p(c.ctypes.data), PC_MEM_HOST, e.shape[0], (e, c)
+    pe, we = _ptr(exps)
+    pc_, wc = _ptr(coeffs)
+    assert we == wc == PC_MEM_DEVICE and n_terms is not None
+    return pe, pc_, PC_MEM_DEVICE, n_terms, None
 
 
 class Context:
@@ -425,6 +484,38 @@ class Context:
         out = (C.c_uint * 2)()
         self.check(self.lib.pc_hip_last_skzg_launches(self.h, out))
         return int(out[0]), int(out[1])
+
+    # ---- MarlinPST13: the dense lexicographic layout (include/pc_hip.h) -------------------------------
+    def pst13_monomial_evals(self, curve, num_vars, degree, betas, out_dev):
+        """pc_hip_pst13_monomial_evals: out_dev[rank(e)] = prod_j betas[j]^e_j for all M ranks; betas: (num_vars, 4) uint64"""
+        b = np.ascontiguousarray(betas, dtype=np.uint64)
+        assert b.shape == (num_vars, 4)
+        self.check(self.lib.pc_hip_pst13_monomial_evals(self.h, CURVES[curve], num_vars, degree, C.c_void_p(b.ctypes.data), C.c_void_p(out_dev)))
+
+    def pst13_scatter(self, curve, num_vars, degree, exps, coeffs, out_dev, n_terms=None):
+        """pc_hip_pst13_scatter: the terms (exps (T, num_vars) uint8, coeffs (T, 4) uint64; or device pointers with n_terms) into the
+        dense device vector out_dev of M elements"""
+        pe, pc_, where, count, keep = _pst13_terms(num_vars, exps, coeffs, n_terms)
+        self.check(self.lib.pc_hip_pst13_scatter(self.h, CURVES[curve], num_vars, degree, pe, pc_, where, count, C.c_void_p(out_dev)))
+        del keep
+
+    def pst13_divide(self, curve, num_vars, degree, poly, point, quotients_dev, capacity):
+        """pc_hip_pst13_divide: the num_vars quotients of divide_at_point packed into quotients_dev.  poly: (M, 4) uint64 host array or
+        a device pointer; point: (num_vars, 4).  Returns (element offsets, p(z) as (4,) uint64)."""
+        pp, where = _ptr(poly)
+        z = np.ascontiguousarray(point, dtype=np.uint64)
+        assert z.shape == (num_vars, 4)
+        offs = (C.c_size_t * num_vars)()
+        value = np.zeros(4, dtype=np.uint64)
+        self.check(self.lib.pc_hip_pst13_divide(self.h, CURVES[curve], num_vars, degree, pp, where, C.c_void_p(z.ctypes.data), C.c_void_p(quotients_dev),
+                                                capacity, offs, C.c_void_p(value.ctypes.data)))
+        return list(offs), value
+
+    def last_pst13_shape(self):
+        """the last pst13_open: (univariate route?, [pairs of MSM 0, 1, ..]) (pc_hip_last_pst13_shape)"""
+        out = (C.c_uint32 * (2 + PST13_MAX_VARS))()
+        self.check(self.lib.pc_hip_last_pst13_shape(self.h, out))
+        return bool(out[1]), [int(v) for v in out[2:2 + int(out[0])]]
 
     # ---- IPA round primitives (device-resident vectors; `dev` = raw device pointer) --------------
     def fr_fold(self, curve, lo_dev, hi_dev, n_half, s):
@@ -705,6 +796,38 @@ class Srs:
                                                             C.c_void_p(z.ctypes.data), k, C.c_void_p(et.ctypes.data), C.c_void_p(rem.ctypes.data),
                                                             C.c_void_p(out.ctypes.data), C.byref(inf)))
         return rem, out, bool(inf.value)
+
+    def pst13_commit(self, num_vars, degree, dense=None, exps=None, coeffs=None, n_terms=None, base_offset=0):
+        """MarlinPST13::commit without hiding (pc_hip_pst13_commit) of a dense vector ((M, 4) uint64 host array or a device pointer) or
+        of terms (as Context.pst13_scatter).  Returns (xy, is_infinity)."""
+        pd, wd = _ptr(dense) if dense is not None else (None, PC_MEM_HOST)
+        pe, pc_, wt, count, keep = _pst13_terms(num_vars, exps, coeffs, n_terms)
+        out, inf = self._point_out()
+        self.ctx.check(self.ctx.lib.pc_hip_pst13_commit(self.ctx.h, self.h, base_offset, num_vars, degree, pd, wd, pe, pc_, wt, count,
+                                                        C.c_void_p(out.ctypes.data), C.byref(inf)))
+        del keep
+        return out, bool(inf.value)
+
+    def pst13_open(self, num_vars, degree, point, dense=None, exps=None, coeffs=None, n_terms=None, base_offset=0):
+        """MarlinPST13::open without hiding (pc_hip_pst13_open).  Returns ((num_vars, 2*Fq limbs) points w_i, (num_vars,) infinity flags,
+        p(point) as (4,) uint64)."""
+        pd, wd = _ptr(dense) if dense is not None else (None, PC_MEM_HOST)
+        pe, pc_, wt, count, keep = _pst13_terms(num_vars, exps, coeffs, n_terms)
+        z = np.ascontiguousarray(point, dtype=np.uint64)
+        assert z.shape == (num_vars, 4)
+        out = np.zeros((num_vars, 2 * FQ_BYTES[self.curve] // 8), dtype=np.uint64)
+        inf = (C.c_int * num_vars)()
+        value = np.zeros(4, dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.pc_hip_pst13_open(self.ctx.h, self.h, base_offset, num_vars, degree, pd, wd, pe, pc_, wt, count,
+                                                      C.c_void_p(z.ctypes.data), C.c_void_p(out.ctypes.data), inf, C.c_void_p(value.ctypes.data)))
+        del keep
+        return out, np.array(list(inf), dtype=bool), value
+
+    def pst13_trim(self, num_vars, degree, supported_degree, base_offset=0):
+        """MarlinPST13::trim's selection (pc_hip_pst13_trim): a new key in the layout (num_vars, supported_degree)"""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pc_hip_pst13_trim(self.ctx.h, self.h, base_offset, num_vars, degree, supported_degree, C.byref(h)))
+        return Srs._adopt(self.ctx, self.curve, h, pst13_key_len(num_vars, supported_degree))
 
     def msm_many(self, scalars, m=None, n_msms=None, base_offset=0, montgomery=False):
         """n_msms MSMs of m pairs over bases[base_offset : base_offset + m] (pc_hip_msm_many; Hyrax's

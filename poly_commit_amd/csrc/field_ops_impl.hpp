@@ -9,6 +9,7 @@
 #include "hash.hpp"
 #include "sprs.hpp"
 #include "skzg.hpp"
+#include "pst13.hpp"
 
 namespace pc {
 
@@ -109,9 +110,23 @@ struct FieldOpsImpl {
   static uint32_t div_multi_f(HipBackend& be, const SkzgDivLevel* lv, size_t count, const uint32_t* z, uint32_t k, uint32_t* rem, void* scratch, uint32_t fan) {
     return div_multi<FrP>(be, lv, count, z, k, rem, scratch, fan);
   }
+  static void pst13_monomials_f(HipBackend& be, const uint32_t* table, uint32_t n, uint32_t d, size_t len, const uint32_t* pw, uint32_t* out) {
+    Pst13MonomialBody<FrP> b{pw, out, n, d};
+    pst13_launch(be, b, len, table, (n + 1) * (d + 1));
+  }
+  static void pst13_write_f(HipBackend& be, const uint32_t* table, uint32_t n, uint32_t d, const uint8_t* exps, const uint32_t* coeffs, size_t terms,
+                            const uint32_t* owner, uint32_t* flags, uint32_t* out) {
+    Pst13WriteBody<FrP> b{exps, coeffs, owner, flags, out, n, d};
+    pst13_launch(be, b, terms, table, (n + 1) * (d + 1));
+  }
+  static const uint32_t* pst13_divide_f(HipBackend& be, const uint32_t* table, const uint32_t* T_host, uint32_t n, uint32_t d, const uint32_t* p,
+                                        const uint32_t* z, uint32_t* quot, const uint64_t* offs, uint32_t* ping, uint32_t* pong) {
+    return pst13_divide<FrP>(be, table, T_host, n, d, p, z, quot, offs, ping, pong);
+  }
   static FieldOps table() {
     return FieldOps{&make_ntt, &poly_eval_f, &div_scan_f, &witness_f, &fr_fold, &fr_dot, &ipa_fold_dots, &fr_powers, &ipa_key_scalars, &fr_lincomb, &column_hash,
-                    &column_hash_part, &brakedown_encode_f, &brakedown_points<FrP>, &fold_tree_f, &div_multi_f};
+                    &column_hash_part, &brakedown_encode_f, &brakedown_points<FrP>, &fold_tree_f, &div_multi_f,
+                    &pst13_monomials_f, &pst13_write_f, &pst13_divide_f};
   }
 };
 

@@ -49,6 +49,7 @@ struct pc_ctx {
   std::vector<struct pc_lincode*> codes;   // every Brakedown code object of this context that is alive; abi_lincode.hip alone creates and releases them
   float brakedown_phases[4] = {0, 0, 0, 0};
   uint32_t skzg_launches[2] = {0, 0};      // kernel launches of the last streaming_kzg call: [folding tree, divisions + combination] (pc_hip_last_skzg_launches)
+  uint32_t pst13_shape[2 + 32] = {0};      // the last pc_hip_pst13_open: [MSMs, 1 = the univariate route, pairs of MSM 0, 1, ..] (pc_hip_last_pst13_shape)
 };
 
 // What a key of either group is: n affine points resident on the device, registered in its context

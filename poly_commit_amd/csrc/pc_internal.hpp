@@ -3,7 +3,7 @@
 // The library is built from several .hip files compiled in parallel (poly_commit_amd/build.py):
 //   abi_<subject>.hip  the extern "C" entry points (include/pc_hip.h), one unit per subject: ctx (context, errors, memory, timing),
 //                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa, lincode (the Brakedown code object),
-//                      skzg (streaming_kzg: folding tree, multi-point openings); staging,
+//                      skzg (streaming_kzg: folding tree, multi-point openings), pst13 (MarlinPST13: layout, commit, open); staging,
 //                      error translation
 //   key.hpp            host only: the key objects -- pc_key_base and what G1 and G2 keys share over it (fill, read-back, registry,
 //                      locked free), pc_srs with its pipelines and the derived keys of an opening, pc_g2_srs -- their whole lifetime
@@ -15,7 +15,8 @@
 //   host_tail.hpp      host only: 64-bit-limb points of either group -- the MSM's Horner tail, affine -> XYZZ, one scalar
 //                      multiplication, a sum of points, the fixed base's window table
 //   field_<name>.hip   everything templated on one scalar field: NTT, division scan, IPA vector kernels,
-//                      column digests, the Brakedown encoder (sprs.hpp), the folding tree and multi-point division (skzg.hpp)
+//                      column digests, the Brakedown encoder (sprs.hpp), the folding tree and multi-point division (skzg.hpp),
+//                      MarlinPST13's monomial evaluations, scatter and division along a variable (pst13.hpp)
 // The abi units reach the templates through the two tables of plain function pointers below, one
 // instance per curve / field.
 #pragma once
@@ -124,6 +125,15 @@ struct FieldOps {
   uint32_t (*fold_tree)(HipBackend& be, const uint32_t* f, size_t n, const uint32_t* rho_host, uint32_t depth, uint32_t* out, const uint64_t* offs_host);
   uint32_t (*div_multi)(HipBackend& be, const SkzgDivLevel* lv, size_t count, const uint32_t* z_host, uint32_t k, uint32_t* rem_host, void* scratch,
                         uint32_t fan);
+  // MarlinPST13 (pst13.hpp), on the layout (n, d) with its table T of (n + 1)(d + 1) words on the device.  None drains the stream.
+  // out[rank] = prod_j pw[j][e_j] for every rank; pw: n x (d + 1) powers on the device
+  void (*pst13_monomials)(HipBackend& be, const uint32_t* table, uint32_t n, uint32_t d, size_t len, const uint32_t* pw, uint32_t* out);
+  // the second pass of the scatter: every term that owns its slot writes its coefficient, the others raise PST13_FLAG_REPEATED
+  void (*pst13_write)(HipBackend& be, const uint32_t* table, uint32_t n, uint32_t d, const uint8_t* exps, const uint32_t* coeffs, size_t terms,
+                      const uint32_t* owner, uint32_t* flags, uint32_t* out);
+  // the n passes of the division (n >= 2): see pst13_divide; returns the device buffer whose slot 0 holds p(z)
+  const uint32_t* (*pst13_divide)(HipBackend& be, const uint32_t* table, const uint32_t* T_host, uint32_t n, uint32_t d, const uint32_t* p,
+                                  const uint32_t* z_host, uint32_t* quot, const uint64_t* offs, uint32_t* ping, uint32_t* pong);
 };
 
 // (accessor functions rather than global tables: a namespace-scope constant would also be emitted into the

@@ -31,8 +31,8 @@ struct Bls12_377 { typedef pc_curve_bls12_377 C; static constexpr pc_curve ID = 
 
 // Error variants of poly-commit/src/error.rs that this path can raise.
 struct Error {
-  enum Kind { None, MissingRng, TooManyCoefficients, HidingBoundIsZero, HidingBoundToolarge, UnsupportedDegreeBound, InvalidParameters, IncorrectInputLength, InvalidNumberOfVariables, IncorrectCommitmentSize, InvalidCommitment, TrimmingDegreeTooLarge, MissingPolynomial, EquationHasDegreeBounds, Backend } kind = None;
-  size_t a = 0, b = 0;      // (num_coefficients, num_powers) / (hiding_poly_degree, num_powers) / bound
+  enum Kind { None, MissingRng, TooManyCoefficients, HidingBoundIsZero, HidingBoundToolarge, UnsupportedDegreeBound, InvalidParameters, IncorrectInputLength, InvalidNumberOfVariables, IncorrectCommitmentSize, InvalidCommitment, TrimmingDegreeTooLarge, MissingPolynomial, EquationHasDegreeBounds, Backend, PolynomialDegreeTooLarge } kind = None;
+  size_t a = 0, b = 0;      // (num_coefficients, num_powers) / (hiding_poly_degree, num_powers) / bound / (poly_degree, supported_degree; msg = label)
   std::string msg;          // Backend: pc_hip_strerror / pc_hip_last_error
   explicit operator bool() const { return kind != None; }
 };

@@ -34,12 +34,15 @@ GROUPS = [
      ["pc_hip_ml_eq_evals", "pc_hip_g2_fixed_base_batch_mul", "pc_hip_g2_srs_device_ptr", "pc_hip_ml_setup", "pc_hip_ml_trim"]),
     ("streaming_kzg: FoldedPolynomialTree (streaming_kzg/data_structures.rs:12-138), open_multi_points (space.rs:98-136, time.rs:126-137), batch_open_multi_points (time.rs:141-152), commit_folding / open_folding (space.rs:165-262)",
      ["pc_hip_fold_tree", "pc_hip_poly_div_multi", "pc_hip_kzg_open_multi", "pc_hip_kzg_batch_open_multi", "pc_hip_kzg_commit_folding", "pc_hip_kzg_open_folding"]),
+    ("MarlinPST13 in the dense lexicographic layout: powers_of_beta of setup (marlin_pst13_pc/mod.rs:187-207), divide_at_point (:44-92), commit (:353-362), open (:419-512), trim's selection (:283-288); the layout helpers sort a BTreeMap key into device order",
+     ["pc_hip_pst13_key_len", "pc_hip_pst13_rank", "pc_hip_pst13_unrank", "pc_hip_pst13_monomial_evals", "pc_hip_pst13_scatter", "pc_hip_pst13_divide", "pc_hip_pst13_commit",
+      "pc_hip_pst13_open", "pc_hip_pst13_trim"]),
     ("one committer key over the GPUs of a node, one process",
      ["pc_hip_group_create", "pc_hip_group_destroy", "pc_hip_group_size", "pc_hip_group_ctx", "pc_hip_group_srs_upload", "pc_hip_group_srs_free",
       "pc_hip_group_srs_len", "pc_hip_group_msm", "pc_hip_group_msm_batch", "pc_hip_group_kzg_open", "pc_hip_group_commit_open_async", "pc_hip_group_job_wait", "pc_hip_group_ntt_batch", "pc_hip_group_ligero_commit"]),
     ("measurement and tuning hooks (bench.py, tests); a prover does not need them",
      ["pc_hip_set_msm_tuning", "pc_hip_set_timing", "pc_hip_last_msm_phases_ms", "pc_hip_last_msm_marks_ms", "pc_hip_last_msm_shape",
-      "pc_hip_last_ntt_phases_ms", "pc_hip_last_ligero_phases_ms", "pc_hip_last_brakedown_phases_ms", "pc_hip_last_skzg_launches"]),
+      "pc_hip_last_ntt_phases_ms", "pc_hip_last_ligero_phases_ms", "pc_hip_last_brakedown_phases_ms", "pc_hip_last_skzg_launches", "pc_hip_last_pst13_shape"]),
 ]
 HEAD = '''//! Raw declarations of the C ABI of `libpc_hip.so` (`include/pc_hip.h`): one `extern "C"` symbol per call the shim
 //! replaces in the reference.  GENERATED by tools/gen_ffi_rs.py from the header; `tools/check_ffi_decls.py` (run by the
