@@ -31,7 +31,7 @@ extern "C" int emu_brakedown_validate(size_t msg_len, size_t codeword_len, size_
   return pc::brakedown_validate(msg_len, codeword_len, n_levels, dims, ind_ptr, col_ind, nnz, nullptr);
 }
 
-// field: 0 BLS12-381 Fr, 1 BN254 Fr, 2 Pallas Fr (pc_curve).  Returns the validation's answer; only a valid code is encoded.
+// field: 0 BLS12-381 Fr, 1 BN254 Fr, 2 Pallas Fr, 3 BLS12-377 Fr (pc_curve).  Returns the validation's answer; only a valid code is encoded.
 extern "C" int emu_brakedown_encode(int field, size_t msg_len, size_t codeword_len, size_t n_levels, const size_t* dims, const size_t* ind_ptr,
                                     const uint32_t* col_ind, const uint32_t* val, size_t nnz, const uint32_t* msgs, uint32_t rows, uint32_t* out) {
   pc::BrakedownLayout L;
@@ -39,5 +39,6 @@ extern "C" int emu_brakedown_encode(int field, size_t msg_len, size_t codeword_l
   if (rc) return rc;
   if (field == 0) return encode_t<pc_bls12_381_fr>(L, ind_ptr, col_ind, val, msgs, rows, out);
   if (field == 1) return encode_t<pc_bn254_fr>(L, ind_ptr, col_ind, val, msgs, rows, out);
+  if (field == 3) return encode_t<pc_bls12_377_fr>(L, ind_ptr, col_ind, val, msgs, rows, out);
   return encode_t<pc_pallas_fr>(L, ind_ptr, col_ind, val, msgs, rows, out);
 }

@@ -21,7 +21,7 @@ import pyref as R
 
 ALPHA, BETA, RHO_INV, BASE_LEN, SEC_PARAM = (178, 1000), (61, 1000), (1521, 1000), 30, 128      # brakedown.rs:111-115
 M64 = (1 << 64) - 1
-FIELD_ID = {"bls12_381": 0, "bn254": 1, "pallas": 2}          # pc_curve
+FIELD_ID = {"bls12_381": 0, "bn254": 1, "pallas": 2, "bls12_377": 3}          # pc_curve
 TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROOT = os.path.dirname(TESTS)
 _R = 1 << 256
@@ -31,8 +31,19 @@ class InvalidCommitment(ValueError):
     """linear_codes Error::InvalidCommitment."""
 
 
+def ref_of(curve):
+    """The Python reference that knows the curve: the shared `pyref` for its three curves, the private copy of
+    tests/harness/ref377.py for BLS12-377 (the shared module is not taught the fourth curve)."""
+    if curve in R.CURVES:
+        return R
+    from harness import ref377
+    assert curve == ref377.CURVE
+    return ref377.R
+
+
 def field_p(curve):
-    return R.FIELDS[R.CURVES[curve]["fr"]]["p"]
+    ref = ref_of(curve)
+    return ref.FIELDS[ref.CURVES[curve]["fr"]]["p"]
 
 
 def monts(curve, vals):
@@ -316,26 +327,30 @@ def num_queries(curve, m_ext):
 
 def tensor(curve, point, left_len):
     """MultilinearBrakedown::tensor (mod.rs:96-107): the point split at log2(left_len)."""
-    return R.ligero_multilinear_tensor(R.CURVES[curve]["fr"], point, left_len)
+    ref = ref_of(curve)
+    return ref.ligero_multilinear_tensor(ref.CURVES[curve]["fr"], point, left_len)
 
 
 def ref_commit(code, n_rows, evals, col_hash="blake2s", tree_hash="sha256", len_prefix=True):
-    fr = R.CURVES[code.curve]["fr"]
+    ref = ref_of(code.curve)
+    fr = ref.CURVES[code.curve]["fr"]
     flat = list(evals) + [0] * (n_rows * code.m - len(evals))
     mat = [flat[r * code.m:(r + 1) * code.m] for r in range(n_rows)]
     ext = [encode(code, row) for row in mat]
-    leaves = [R.column_digest(fr, [ext[r][j] for r in range(n_rows)], col_hash) for j in range(code.m_ext)]
-    nodes = R.merkle_tree(leaves, tree_hash, len_prefix)
+    leaves = [ref.column_digest(fr, [ext[r][j] for r in range(n_rows)], col_hash) for j in range(code.m_ext)]
+    nodes = ref.merkle_tree(leaves, tree_hash, len_prefix)
     return dict(n_rows=n_rows, n_cols=code.m, n_ext_cols=code.m_ext, root=nodes[0], mat=mat, ext=ext, leaves=leaves, nodes=nodes)
 
 
 def ref_open(code, st, indices, r, tensors):
-    return R.ligero_open(R.CURVES[code.curve]["fr"], st, None, indices, r, tensors=tensors)
+    ref = ref_of(code.curve)
+    return ref.ligero_open(ref.CURVES[code.curve]["fr"], st, None, indices, r, tensors=tensors)
 
 
 def ref_check(code, commitment, value, proof, indices, r, tensors, col_hash="blake2s", tree_hash="sha256"):
     """LinearCodePCS::check (:375-503); raises InvalidCommitment where the reference returns Err, False for a wrong value."""
-    fr, p = R.CURVES[code.curve]["fr"], code.p
+    ref = ref_of(code.curve)
+    fr, p = ref.CURVES[code.curve]["fr"], code.p
     n_rows, n_cols, n_ext, t = commitment["n_rows"], commitment["n_cols"], commitment["n_ext_cols"], len(indices)
     if (r is not None) != (proof["well_formedness"] is not None):
         raise InvalidCommitment("well-formedness")
@@ -343,7 +358,7 @@ def ref_check(code, commitment, value, proof, indices, r, tensors, col_hash="bla
             or any(not 0 <= i < n_ext for i in indices) or (r is not None and (len(proof["well_formedness"]) != n_cols or len(r) != n_rows))):
         raise InvalidCommitment("proof shape")
     for col, q_j, (idx, sib, path) in zip(proof["columns"], indices, proof["paths"]):
-        if idx != q_j or not R.merkle_verify(commitment["root"], R.column_digest(fr, col, col_hash), idx, sib, path, tree_hash):
+        if idx != q_j or not ref.merkle_verify(commitment["root"], ref.column_digest(fr, col, col_hash), idx, sib, path, tree_hash):
             raise InvalidCommitment("path")
     w = encode(code, proof["v"])
     a, b = tensors
@@ -364,6 +379,7 @@ def commit(ctx, code, dev_code, n_rows, evals_dev, col_hash="blake2s", tree_hash
     mat = torch.zeros((n_rows * code.m, 4), dtype=torch.int64, device=evals_dev.device)
     mat[:evals_dev.shape[0]] = evals_dev
     ext = torch.empty((n_rows * code.m_ext, 4), dtype=torch.int64, device=evals_dev.device)
+    torch.cuda.synchronize()                                      # torch's fill and copy are only queued; the library's streams do not wait for them
     nodes, leaves = dev_code.commit(mat, rows=n_rows, col_hash=col_hash, tree_hash=tree_hash, len_prefix=len_prefix, ext_out=ext)
     com = dict(n_rows=n_rows, n_cols=code.m, n_ext_cols=code.m_ext, root=bytes(nodes[0]))
     return com, dict(mat=mat, ext=ext, leaves=leaves, nodes=nodes, **com)

@@ -151,3 +151,106 @@ def test_lazy_flags_come_from_the_modulus(host):
         assert f.lazy and f.lazy_fused
         assert host.raw("pc_probe_field_lazy_bls12_377", P.C.c_int(f.which)) == 3
     assert host.raw("pc_probe_field_lazy_store_bls12_377", P.C.c_int(0)) == 1
+
+
+# ---- the checkers of the IPA / protocol GPU tests (tests/harness/ipa377.py, tests/harness/brakedown.py on the fourth field) --------
+
+@pytest.mark.parametrize("n,zero_at", [(2, None), (4, 2), (16, None), (16, 9)])
+def test_ipa_rounds_over_logarithms_equal_the_copy_on_points(n, zero_at):
+    """ipa_rounds_dlog's logarithms times G are R.ipa_rounds on the real points P_i = d_i G, d_i = i + 1 -- one case per size with a
+    generator at infinity (d_i = 0)"""
+    from harness import ipa377 as I
+    pts, _ = B.gen_bases(n + 1)
+    d = [i + 1 for i in range(n)]
+    key = list(pts[:n])
+    if zero_at is not None:
+        d[zero_at], key[zero_at] = 0, None
+    h_log = n + 1
+    coeffs = R.gen_scalars(B.FR, 0x1A0 + n, n)
+    coeffs[n // 2] = 0
+    z = R.gen_scalars(B.FR, 0x1A1, 1)[0]
+    ch = R.gen_scalars(B.FR, 0x1A2 + n, n.bit_length() - 1)
+    want_l, want_r, want_key, want_c = R.ipa_rounds(B.CURVE, key, coeffs, z, pts[n], ch)
+    l, r_, k, c = I.ipa_rounds_dlog(d, h_log, coeffs, z, ch)
+    g = lambda e: B.mul_g(e) if e else None                                  # noqa: E731
+    assert [g(e) for e in l] == want_l and [g(e) for e in r_] == want_r and g(k) == want_key and c == want_c
+    assert (I.log_points(l) == B.points(want_l)).all()
+
+
+def test_fold_case_is_the_fold_of_its_key():
+    """fold_case: the expected points (an addition chain, special lanes by mul_g) are K_l[i] + u K_r[i] of the key its logarithms
+    describe, computed the slow way on points"""
+    from harness import ipa377 as I
+    half = 12
+    for u in (0, 1, B.RMOD - 1, I.glv_constants()["lam"], 0x1234567 << 200):
+        specials = dict(zip((1, 3, 5, 7, 9), I.SPECIAL_LANES))
+        d, want, e, delta = I.fold_case(half, u, 0xF0 + half, specials)
+        assert e[2] == (e[0] + 2 * delta) % B.RMOD and e[9] == 0
+        pts = [B.mul_g(x) if x else None for x in d]
+        assert pts[1] is None and pts[half + 3] is None and pts[5] is None and pts[half + 5] is None
+        got = [R.ec_add(B.CURVE, pts[i], R.ec_mul(B.CURVE, u, pts[half + i]) if u else None) for i in range(half)]
+        assert got == want, hex(u)
+        assert want[9] is None and (u == 0 or want[7] == R.ec_add(B.CURVE, pts[7], pts[7]))
+    d, want, _, _ = I.fold_case(5, 7, 1, inf_lo=1, inf_hi=2)
+    assert d[1] == 0 and d[5 + 2] == 0 and want[2] == B.mul_g(d[2]) and want[1] == B.mul_g(7 * d[5 + 1])
+    some, zeros = I.check_positions(d)
+    assert some[0] == 0 and some[-1] == 9 and len(some) == 4 and zeros == [1, 7]
+
+
+def test_glv_split_in_python_and_the_longest_split():
+    """glv_split restates glv_decompose (the same arithmetic as test_glv_constants); the seeded search for the challenge with the
+    longest halves finds 127 bits -- inside GLV_HALF_BITS = 130 and the fold table's 131 rows (NAF digits at bits 0 .. 127)"""
+    from harness import ipa377 as I
+    g = I.glv_constants()
+    lam = g["lam"]
+    assert (lam * lam + lam + 1) % B.RMOD == 0
+    for name, k in I.edge_challenges():
+        k1, k2 = I.glv_split(k, g)
+        assert (k1 + k2 * lam - k) % B.RMOD == 0 and max(abs(k1), abs(k2)).bit_length() <= 130, name
+    k, bits = I.longest_split()
+    assert bits == 127 and 0 < k < B.RMOD
+    assert max(abs(x) for x in I.glv_split(k, g)).bit_length() == 127
+    # The basis of this curve puts every split on one side.  With truncated quotients the remainder is f1 v1 + f2 v2, f1, f2 in [0, 1),
+    # of the basis vectors v1 = (a1, b1) = (1, -|b1|), v2 = (a2, b2) = (|a2|, 1): k1 = f1 + f2 |a2| >= 0, and k2 = f2 - f1 |b1| < 1 is an
+    # integer, so k2 <= 0.  EcFoldGlvBody's neg1 is therefore never set on this curve, and neg2 whenever k2 != 0 -- asserted for the
+    # edge challenges and the 4000 seeded values.
+    assert g["a1"] == 1 and g["b1"] < 0 and g["a2"] > 0 and g["b2"] == 1
+    assert all(k1 >= 0 >= k2 for k1, k2 in (I.glv_split(k, g) for k in [u for _, u in I.edge_challenges()] + I.seeded_challenges()))
+    # the other curves' constants parse the same way (the edge-challenge fold test runs on BLS12-381 and Pallas too)
+    for curve, fr in (("bls12_381", "bls12_381_fr"), ("pallas", "pallas_fr")):
+        p = pyref.FIELDS[fr]["p"]
+        gc = I.glv_constants(curve)
+        assert (gc["lam"] ** 2 + gc["lam"] + 1) % p == 0
+        for name, k in I.edge_challenges(p, curve):
+            k1, k2 = I.glv_split(k, gc)
+            assert 0 <= k < p and (k1 + k2 * gc["lam"] - k) % p == 0 and max(abs(k1), abs(k2)).bit_length() <= 130, (curve, name)
+
+
+def test_brakedown_harness_on_the_fourth_field():
+    """tests/harness/brakedown.py with BLS12-377's Fr: the modulus comes from the private copy, the encode is linear and systematic,
+    the clipped concurrent form equals the reference's loop, the base code is its definition, and the kernel bodies of csrc/sprs.hpp
+    instantiated for pc_bls12_377_fr and stepped lane by lane give the same codewords -- rows of all r - 1 and all 0 included"""
+    from harness import brakedown as BD
+    import test_brakedown_cpu as TB
+    assert BD.FIELD_ID[B.CURVE] == 3 and BD.field_p(B.CURVE) == B.RMOD and BD.ref_of(B.CURVE) is R and BD.ref_of("bn254") is pyref
+    p = B.RMOD
+    _, code = BD.default_code(B.CURVE, 10, 0x377B)
+    assert code.p == p and all(0 < v < p for mt in code.a_mats + code.b_mats for v in mt.val)
+    x, y = BD.messages(code, 2, 31)
+    a, b = BD.Gen(77).nonzero(p), BD.Gen(78).nonzero(p)
+    ex, ey = BD.encode(code, x), BD.encode(code, y)
+    assert ex[:code.m] == x and len(ex) == code.m_ext
+    assert BD.encode(code, [(a * u + b * v) % p for u, v in zip(x, y)]) == [(a * u + b * v) % p for u, v in zip(ex, ey)]
+    levels = list(range(len(code.start)))
+    assert BD.encode(code, x, b_order=levels[::-1], clip=True) == ex
+    base = BD.base_code(B.CURVE, 17)
+    m17 = BD.messages(base, 1, 5)[0]
+    assert BD.encode(base, m17) == [sum(c * pow(k, i, p) for i, c in enumerate(m17)) % p for k in range(1, 27)]
+    for cd in (code, BD.ragged_code(B.CURVE), base):
+        msgs = BD.messages(cd, 3, 9) + [[p - 1] * cd.m, [0] * cd.m]
+        want = [BD.encode(cd, m) for m in msgs]
+        assert want[-1] == [0] * cd.m_ext
+        assert TB.emu_encode(cd, msgs) == want, cd.m
+    # the commitment's digests go through the copy's column_digest (the field's byte length)
+    st = BD.ref_commit(base, 2, m17 + m17)
+    assert st["leaves"][3] == R.column_digest(B.FR, [st["ext"][0][3], st["ext"][1][3]], "blake2s")

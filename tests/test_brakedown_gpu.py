@@ -27,6 +27,7 @@ def dev_encode_device(code, dev_code, msgs):
     flat = B.monts(code.curve, [x for row in msgs for x in row]).reshape(len(msgs), code.m, 4)
     x = torch.from_numpy(np.ascontiguousarray(flat).view(np.int64)).cuda()
     y = torch.full((len(msgs), code.m_ext, 4), -1, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()      # torch's fill is only queued and the library's streams do not wait for torch's: finish it before the library writes
     dev_code.encode(x, rows=len(msgs), out=y)
     torch.cuda.synchronize()
     return y.cpu().numpy().view(np.uint64)

@@ -81,6 +81,7 @@ def make_key(ctx, curve, n, d):
         _release_keys()
         c, M = cv(curve), H.key_len(n, d)
         ev = torch.full((M + 1, 4), -1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()      # torch's fill is only queued and the library's streams do not wait for torch's: finish it before the library writes
         ctx.pst13_monomial_evals(curve, n, d, c.mont(_betas(curve, n)), ev.data_ptr())
         pts = torch.empty((M, 2 * c.limbs), dtype=torch.int64, device="cuda")
         ctx.fixed_base_batch_mul(curve, c.point(1), ev.data_ptr(), M, pts.data_ptr())
@@ -172,6 +173,7 @@ def test_scatter(ctx, curve, n, d):
         want = c.mont(H.to_dense(poly, n, d, c.p))
         for on_device in (False, True):
             out = torch.full((M + 1, 4), -1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
             if on_device and len(poly):
                 e_dev, c_dev = torch.from_numpy(exps.copy()).cuda(), _dev(co)
                 ctx.pst13_scatter(curve, n, d, e_dev, c_dev, out.data_ptr(), n_terms=len(poly))
@@ -214,6 +216,7 @@ def test_divide(ctx, curve, n, d):
         src = c.mont(vec)
         for inp in (src, _dev(src)):
             quot = torch.full((total + 1, 4), -1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()
             offs, val = ctx.pst13_divide(curve, n, d, inp if isinstance(inp, np.ndarray) else inp.data_ptr(), c.mont(z), quot.data_ptr(), total)
             assert offs == [sum(prefix[:i]) for i in range(n)]   # the offsets are the prefix lengths, summed
             got = quot.cpu().numpy().view(np.uint64)
@@ -308,6 +311,20 @@ def test_bls12_377_commit_and_open(ctx):
     assert c.ints(val) == [value] and not inf.any()
     for i in range(n):
         assert (got[i] == c.point(dot(ws[i], mv, c.p))).all(), i
+
+
+@pytest.mark.parametrize("n,d", [(3, 4), (3, 17)])
+def test_bls12_377_setup_scatter_and_divide(ctx, n, d):
+    """pc_hip_pst13_monomial_evals, _scatter and _divide called directly for BLS12-377: the checks of the three tests above, every word,
+    at M = 35 and at M = 1140 (more than one workgroup, fibers of lengths 1 .. 18)"""
+    test_setup_monomial_evaluations_and_key_points(ctx, "bls12_377", n, d)
+    test_scatter(ctx, "bls12_377", n, d)
+    test_divide(ctx, "bls12_377", n, d)
+
+
+def test_bls12_377_trim(ctx):
+    """pc_hip_pst13_trim for BLS12-377, on a key whose points test_bls12_377_setup_scatter_and_divide compares with the trapdoor"""
+    test_trim_is_the_key_of_the_smaller_degree(ctx, "bls12_377")
 
 
 # ---- trim -------------------------------------------------------------------------------------------------------------------------

@@ -117,6 +117,7 @@ def test_fold_tree_every_level(ctx, curve, n):
         total = sum(len(lv) for lv in want)
         for src in (fm, _dev(fm)):
             out = torch.full((total + 1, 4), -1, dtype=torch.int64, device="cuda")
+            torch.cuda.synchronize()      # torch's fill is only queued and the library's streams do not wait for torch's: finish it before the library writes
             offs = ctx.fold_tree(curve, src if isinstance(src, np.ndarray) else src.data_ptr(), _mont(curve, rhos), out.data_ptr(), total, n=n)
             assert offs == [sum(len(lv) for lv in want[:i]) for i in range(depth)]
             got = out.cpu().numpy().view(np.uint64)
