@@ -308,6 +308,23 @@ template <class C> struct AccSum { static constexpr bool R30 = false; typedef Xy
 #if PC_ACC_R30
 template <> struct AccSum<pc_curve_bls12_381> { static constexpr bool R30 = true; typedef XyzzR30 type; };
 #endif
+// Where the base of entry p + 1, gathered right before the addition of entry p, waits until that addition is over.  StageRegs: in
+// registers, AffD<C>::WORDS of them live across the whole addition (every host caller, every kernel but the one below).  The
+// radix-2^30 kernel has no register to spare (256 allocated, two waves per SIMD), so there the gather lands in the lane's slot of the
+// workgroup's exchange tile instead (msm_coop.hpp StageLds) and is read back once the addition is over.  A policy provides
+//   gather(src)   issue the gather of the AffD<C>::WORDS words at src
+//   take()        the gathered base (called behind the addition; everything in flight has had the addition to arrive)
+//   done()        behind the chunk's last iteration: nothing of the policy's may be in flight any more
+// The slot of workgroup lane `tid`: its point in pieces of four words, piece j of a wave's 64 lanes contiguous (what one
+// LDS-DMA instruction writes: 16 bytes per lane in lane order; read back with one 16-byte read per lane, conflict-free)
+PC_HD constexpr uint32_t acc_stage_word(uint32_t tid, uint32_t piece, uint32_t pieces) { return ((tid >> 6) * pieces + piece) * 256u + (tid & 63u) * 4u; }
+template <class C>
+struct StageRegs {
+  AffD<C> nxt;
+  PC_HD void gather(const uint32_t* src) { nxt = AffD<C>::load(src); }
+  PC_HD AffD<C> take() const { return nxt; }
+  PC_HD void done() const {}
+};
 template <class C>
 struct AccumulateBody {
   typedef XyzzD<C> Pt;
@@ -345,7 +362,8 @@ struct AccumulateBody {
   }
   // One lane's chunk.  Returns the keys of its (at most two) partial runs -- their points are in
   // slots 2t / 2t+1 -- and, in `last`, the register copy of the last run's sum (valid iff k1 is).
-  PC_HD void chunk(uint32_t t, uint32_t& k0, uint32_t& k1, Pt& last) const {
+  template <class Stage = StageRegs<C>>
+  PC_HD void chunk(uint32_t t, uint32_t& k0, uint32_t& k1, Pt& last, Stage st = Stage()) const {
     const uint32_t M = offsets[g.NB];
     const uint64_t s64 = (uint64_t)t * g.T;
     k0 = KEY_INVALID; k1 = KEY_INVALID;
@@ -392,12 +410,12 @@ struct AccumulateBody {
         // just issued -- s_waitcnt vmcnt(3) / vmcnt(2) right behind the four loads of the 8-limb kernels, a memory round trip in
         // EVERY iteration)
         if constexpr (PREFETCH_PT) {
-        const AffD<C> npt = AffD<C>::load(bases + (size_t)(nval & PC_ACC_DEBUG_IDX_MASK) * g.pt_stride);
+        st.gather(bases + (size_t)(nval & PC_ACC_DEBUG_IDX_MASK) * g.pt_stride);
         const uint32_t nnval = entries[p + 2 < e ? p + 2 : e - 1];
         next_boundary = offsets[k + 2 <= g.NB ? k + 2 : g.NB];
         if constexpr (R30) acc.add_affine(pt, (val >> 31) != 0);
         else if constexpr (LAZY) acc.add_affine_lz(pt, (val >> 31) != 0); else acc.add_affine(pt.neg_if(val >> 31));
-        val = nval; nval = nnval; pt = npt;
+        val = nval; nval = nnval; pt = st.take();
         } else {
           const uint32_t nnval = entries[p + 2 < e ? p + 2 : e - 1];
           next_boundary = offsets[k + 2 <= g.NB ? k + 2 : g.NB];
@@ -406,6 +424,7 @@ struct AccumulateBody {
           pt = AffD<C>::load(bases + (size_t)(val & PC_ACC_DEBUG_IDX_MASK) * g.pt_stride);      // (behind the chunk's end `val` repeats a valid index)
         }
       }
+      st.done();
       // (two spellings of the same tail on purpose: the 32-bit forms keep the statement order they had before the radix-2^30 sum existed, so
       // that a build with PC_ACC_R30=0 stays instruction-identical to it -- the merged form moved two instructions of that kernel)
       if constexpr (R30) {

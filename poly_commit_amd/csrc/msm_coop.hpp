@@ -183,6 +183,47 @@ __global__ void __launch_bounds__(256) k_bucket_level_coop2(uint32_t K, uint32_t
 // (the radix-2^30 running sum, msm.hpp AccSum: held to two waves -- left alone the allocator takes 300 registers and one wave)
 // WG: lanes per workgroup.  The exchange tile holds one XYZZ point per lane: 48 KiB at 256 lanes of 12-limb points; a G2 point is twice
 // that (96 words), so G2 runs workgroups of 128 lanes -- the tile stays 48 KiB, the point stays whole
+// PC_ACC_LDS_STAGE (default 1; 0 builds the register form of every kernel): the radix-2^30 kernel's prefetched base waits in the
+// exchange tile, not in registers (msm.hpp StageRegs).  The tile is idle until the chunk loop ends; the stage uses its first 24 KiB.
+#ifndef PC_ACC_LDS_STAGE
+#define PC_ACC_LDS_STAGE 1
+#endif
+template <class C> struct AccStage { static constexpr bool LDS = PC_ACC_LDS_STAGE && AccSum<C>::R30 && !ScalarCurveOf<C>::IS_G2; };
+// The gather as LDS-DMA: six 16-byte loads per lane with no register destination (gfx950 global_load_lds_dwordx4: the source address
+// is the lane's, the destination is a wave-uniform base + 16 * lane -- the layout of acc_stage_word).  The compiler counts them on the
+// memory counter like any load and waits for them before the reads of take(); done() drains the chunk's last (unused, clamped)
+// gather, so that nothing is still landing in the tile when the workgroup starts to exchange points through it.
+// Two orderings the stage relies on, both inside AccumulateBody::chunk:
+//   * within a lane, gather(p + 2) may overwrite the slot only after the reads of take(p + 1) have RETURNED.  take() is the last statement
+//     of an iteration and the gather comes behind the next iteration's PC_ARRIVED(pt, ..), which names a word of every 16-byte piece of
+//     `pt`: the compiler places s_waitcnt lgkmcnt(0) there, in front of the boundary block and the gather.  A chunk loop that moves
+//     PC_ARRIVED behind the gather, or drops it, needs a wait of its own between take() and gather().
+//   * between lanes, nothing: a lane reads and writes its own slot only (acc_stage_word), so the loop needs no barrier.
+template <class C>
+struct StageLds {
+  typedef __attribute__((address_space(3))) uint32_t lds_u32;
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) u32x4 lds_u128;
+  static constexpr uint32_t PIECES = AffD<C>::WORDS / 4;
+  lds_u32* tile; uint32_t tid;
+  __device__ __forceinline__ void gather(const uint32_t* src) const {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#pragma unroll
+    for (uint32_t j = 0; j < PIECES; j++)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 4 * j),
+                                       (__attribute__((address_space(3))) void*)(tile + acc_stage_word(wave << 6, j, PIECES)), 16, 0, 0);
+  }
+  __device__ __forceinline__ AffD<C> take() const {
+    uint32_t w[AffD<C>::WORDS];
+#pragma unroll
+    for (uint32_t j = 0; j < PIECES; j++) {
+      const u32x4 v = *(const lds_u128*)(tile + acc_stage_word(tid, j, PIECES));
+      w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
+    }
+    return AffD<C>::load(w);
+  }
+  __device__ __forceinline__ void done() const { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+};
 template <class C> struct AccTune {
   static constexpr int WAVES = Fd<typename C::FqP>::N <= 8 ? PC_ACC_WAVES_N8 : (AccSum<C>::R30 && PC_ACC_WAVES_PER_EU < 2) ? 2 : PC_ACC_WAVES_PER_EU;
   static constexpr uint32_t WG = ScalarCurveOf<C>::IS_G2 ? 128u : 256u;
@@ -192,13 +233,23 @@ template <class C>
 __global__ void PC_ACC_BOUNDS k_accumulate(AccumulateBody<C> b, uint32_t lanes) {
   typedef XyzzD<C> Pt;
   constexpr uint32_t WG = AccTune<C>::WG;
-  __shared__ uint32_t xch[Pt::WORDS * WG];
+  __shared__ __attribute__((aligned(AccStage<C>::LDS ? 16 : 4))) uint32_t xch[Pt::WORDS * WG];
   __shared__ uint32_t key_out[WG], key_first[WG], flags[WG];
   const uint32_t tid = threadIdx.x, t = blockIdx.x * WG + tid;
   const bool valid = t < lanes;
   uint32_t k0 = KEY_INVALID, k1 = KEY_INVALID;
   Pt V = Pt::infinity();                       // the lane's last run (AccumulateBody::chunk), then the scanned sum of its chain
+  if constexpr (AccStage<C>::LDS) {
+    // The tile is the stage until the chunk loops end.  A wave's last take() and its done() lie inside chunk(); the FIRST statement
+    // behind it that touches the tile must be behind a workgroup barrier, because other waves may still be in their loops.  Today that
+    // barrier is the __syncthreads_or at the head of the scan loop below (always executed once, before the first lds.put).  Anything
+    // put between here and that barrier -- an lds.put, an early exit of some waves -- breaks the kernel silently: give it a
+    // __syncthreads() of its own right behind this call.
+    static_assert(AffD<C>::WORDS * WG <= Pt::WORDS * WG && WG % 64 == 0, "the stage lies inside the exchange tile");
+    if (valid) b.chunk(t, k0, k1, V, StageLds<C>{(typename StageLds<C>::lds_u32*)xch, tid});
+  } else {
   if (valid) b.chunk(t, k0, k1, V);
+  }
   const uint32_t M = b.offsets[b.g.NB];
   const uint64_t s64 = (uint64_t)t * b.g.T;
   const uint32_t cs = s64 < M ? (uint32_t)s64 : M;
@@ -213,7 +264,7 @@ __global__ void PC_ACC_BOUNDS k_accumulate(AccumulateBody<C> b, uint32_t lanes) 
   uint32_t fl = (okey == KEY_INVALID || !transparent) ? 1u : 0u;
   for (uint32_t d = 1; d < WG; d <<= 1) {
     const bool need = !(fl & 1u);
-    if (!__syncthreads_or(need)) break;
+    if (!__syncthreads_or(need)) break;          // (d == 1: also the barrier between the chunk loops' stage and the tile's first put, see above)
     if (okey != KEY_INVALID) lds.put(tid, V);
     flags[tid] = fl;
     __syncthreads();

@@ -230,6 +230,36 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W, W))
   uint32_t r = 0; for (int i = 0; i < C::FqP::N; i++) r ^= a32.X.l[i] ^ a32.ZZ.l[i];
   out[t] = r;
 }
+// ... and with the live state the accumulate kernel carries beside the sum (msm.hpp AccumulateBody::chunk with the register stage): a
+// next-base buffer of 24 words that stays in registers across the whole addition, beside the current base.  The buffer is fed from a
+// per-lane rotating register copy, not from memory, and is pinned in VGPRs before and behind the addition (empty asm), so the loop
+// stays memory-free and the compiler can neither drop the buffer nor rematerialise it; it enters the hash under a condition that is
+// false at run time, so the lanes compare with the canonical loop like the others.  Bounds as k_accumulate's: 256 lanes, two waves.
+__global__ void __launch_bounds__(256, 2) k_madd30_carry(uint32_t* out, const uint32_t* pts, int npts, int iters) {
+  typedef pc_curve_bls12_381 C;
+  uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  pc::XyzzR30 acc = pc::XyzzR30::infinity();
+  constexpr int AW = 2 * C::FqP::N;
+  uint32_t nb[AW];
+#pragma unroll
+  for (int i = 0; i < AW; i++) nb[i] = t * 0x9E3779B9u + (uint32_t)i;
+  for (int it = 0; it < iters; it++) {
+    pc::AffD<C> p = pc::AffD<C>::load(pts + (size_t)((t * 31 + it) % npts) * AW);
+#pragma unroll
+    for (int i = 0; i < AW; i++) asm volatile("" : "+v"(nb[i]));
+    acc.add_affine(p, false);
+#pragma unroll
+    for (int i = 0; i < AW; i++) asm volatile("" : "+v"(nb[i]));
+    const uint32_t head = nb[0];                 // the rotation: word i takes word i + 1, the head goes to the end changed by this iteration
+#pragma unroll
+    for (int i = 0; i + 1 < AW; i++) nb[i] = nb[i + 1];
+    nb[AW - 1] = head + (uint32_t)it;
+  }
+  const pc::XyzzD<C> a32 = acc.to32().canonical();
+  uint32_t r = 0; for (int i = 0; i < C::FqP::N; i++) r ^= a32.X.l[i] ^ a32.ZZ.l[i];
+  if (iters < 0) { for (int i = 0; i < AW; i++) r ^= nb[i]; }
+  out[t] = r;
+}
 template <class C> struct HasR30 { static constexpr bool value = false; };
 template <> struct HasR30<pc_curve_bls12_381> { static constexpr bool value = true; };
 template <class C>
@@ -273,6 +303,10 @@ static int bench_madd(const char* name, uint32_t* out, int blocks, int threads) 
       float n3 = timeit([&]() { hipLaunchKernelGGL((k_madd30_waves<3>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d30[1]);
       float n4 = timeit([&]() { hipLaunchKernelGGL((k_madd30_waves<4>), dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(d30[2]);
       printf("  the same with the sum in radix 2^30, lanes that differ: %zu / %zu / %zu\n", d30[0], d30[1], d30[2]);
+      { size_t dc = 0;
+        float nc = timeit([&]() { hipLaunchKernelGGL(k_madd30_carry, dim3(blocks), dim3(threads), 0, 0, out, dp, 64, it); }); differing(dc);
+        printf("  radix-2^30 form with a 24-word next-base buffer live across the addition, 2 waves per SIMD: %8.2f M madd/s (beside %8.2f without; lanes that differ: %zu)\n",
+               ops / nc, ops / n2, dc); }
       if (PC_ACC_R30) {
         printf("  radix-2^32 form %-12s at 2 / 3 / 4 waves per SIMD: %8.2f / %8.2f / %8.2f M madd/s\n", name, ops / m2, ops / m3, ops / m4);
         m2 = n2; m3 = n3; m4 = n4;
