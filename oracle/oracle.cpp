@@ -6,7 +6,7 @@
 //
 // Data conventions at this API (they mirror arkworks' in-memory forms):
 //   * field elements ("mont"): Montgomery residues, 64-bit LE limbs (4 per Fr; 6 per
-//     BLS12-381 Fq, 4 per BN254/Pallas Fq)
+//     BLS12-381 / BLS12-377 Fq, 4 per BN254/Pallas Fq)
 //   * bigint scalars ("canon"): canonical residues, 4 x u64 LE  (F::into_bigint())
 //   * affine points: x || y in Montgomery form; the point at infinity is (0, 0)
 //
@@ -189,6 +189,7 @@ static void ntt_inplace(Fp<P>* a, unsigned log_n) {
     case 0: { typedef pc_curve_bls12_381 C; __VA_ARGS__; } break; \
     case 1: { typedef pc_curve_bn254 C; __VA_ARGS__; } break;     \
     case 2: { typedef pc_curve_pallas C; __VA_ARGS__; } break;    \
+    case 3: { typedef pc_curve_bls12_377 C; __VA_ARGS__; } break; \
     default: abort();                                         \
   }
 
@@ -426,7 +427,7 @@ extern "C++" {
 //      (ipa_pc/mod.rs:615-623, 681-688).  ark-serialize / ark-ec 0.5 are not under /root/reference; restated from
 //      their published behaviour:
 //        field element            canonical residue, little-endian, ceil(bits / 8) bytes
-//        short-Weierstrass point  (generic impl: BN254, Pallas)  x as above, then y in ceil((bits + 2) / 8) bytes
+//        short-Weierstrass point  (generic impl: BN254, Pallas, BLS12-377)  x as above, then y in ceil((bits + 2) / 8) bytes
 //                                 with the SWFlags in the top bits of the LAST byte: 0x80 = YIsNegative = y is the larger of
 //                                 {y, -y} (y > -y; YIsPositive, y <= -y, sets no bit), 0x40 = point at infinity (x = y = 0)
 //        BLS12-381 G1             ark-bls12-381 overrides the generic impl with the zcash / IETF encoding:

@@ -1,15 +1,19 @@
 """BLS12-377 for the tests: a PRIVATE copy of the Python reference (oracle/pyref.py) that knows the curve.
 
-The C++ oracle has no BLS12-377 and oracle/ stays as it is, but oracle/pyref.py is generic over its FIELDS / CURVES
+oracle/pyref.py has no BLS12-377 and stays as it is (its golden files with it), but it is generic over its FIELDS / CURVES
 dictionaries.  This module loads that file a second time under another module name and adds the two fields and the curve to the
 copy only: the module every other test imports as `pyref` keeps its three curves (tests/test_bls12_377_cpu.py checks that).
+The C++ oracle does know the curve (id 3): tests/test_oracle_bls12_377_cpu.py holds it against this copy, tests/oracle_lib.py takes
+the curve's moduli from here, and the device tests of the curve check against both.  The host drivers under tests/cpp and the
+workers of poly_commit_amd/sharded.py are not run for the curve.
 
-`R` is the copy; the helpers below turn its Python integers into the C ABI's buffers (little-endian 64-bit limbs, Montgomery form
+`R` is the copy; `edge_keys` / `edge_scalars` are the MSM edge sets both the device and the oracle run; the helpers below turn its Python integers into the C ABI's buffers (little-endian 64-bit limbs, Montgomery form
 where the ABI wants it) and back.  `probe()` is tests/harness/probe.py loaded the same way, with the copy as its reference, so that
 its case tables and checks run for a field it does not list.
 """
 import importlib.util
 import os
+import random
 
 import numpy as np
 
@@ -119,3 +123,30 @@ def mul_g(k):
 def closed_form(scalars, first=1):
     """sum_i k_i P_i for P_i = (first + i) G: one scalar multiplication"""
     return mul_g(sum(k * (first + i) for i, k in enumerate(scalars)))
+
+
+# ---- the edge sets of the MSM tests (the device tests and the C++ oracle's own tests run the same ones) -------------------------------
+
+def edge_keys(n):
+    """(name, discrete logarithms) of the keys of the edge sets; d = 0 is the (0, 0) infinity base, d < 0 a negated point"""
+    plain = [i + 1 for i in range(n)]
+    with_inf = list(plain)
+    with_inf[7] = 0
+    with_inf[min(100, n - 1)] = with_inf[min(100, n - 1) - 1]                        # a repeated base beside its copy
+    same = [7] * n                                                                     # P + P in every bucket that holds two entries
+    pairs = [(i // 2 + 1) * (1 if i % 2 == 0 else -1) for i in range(n)]               # P beside -P
+    return {"plain": plain, "infinity and a repeated base": with_inf, "one base": same, "P beside -P": pairs}
+
+
+def edge_scalars(n, seed):
+    rnd = random.Random(seed)
+    one = rnd.randrange(RMOD)
+    pair_vals = [rnd.randrange(RMOD) for _ in range((n + 1) // 2)]
+    return {
+        "zeros": [0] * n, "ones": [1] * n, "r-1": [RMOD - 1] * n, "alternating 0 and r-1": [0 if i % 2 == 0 else RMOD - 1 for i in range(n)],
+        "one scalar repeated": [one] * n,                                               # one bucket per window spans every chunk
+        "equal in pairs": [pair_vals[i // 2] for i in range(n)],                       # with P beside -P: everything but the last cancels
+        "top window only": [((i % 0x12) + 1) << 248 for i in range(n)],
+        "just below r": [RMOD - 1 - (i << 200) for i in range(n)],                        # the signed digits' carry out of the top window
+        "random": [rnd.randrange(RMOD) for _ in range(n)],
+    }

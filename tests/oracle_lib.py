@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pyref  # noqa: E402
 
-CURVES = {"bls12_381": 0, "bn254": 1, "pallas": 2}
+CURVES = {"bls12_381": 0, "bn254": 1, "pallas": 2, "bls12_377": 3}
 _lib = None
 
 
@@ -48,7 +48,20 @@ def p64(a):
 
 
 def fq_limbs(curve):
-    return 6 if curve == "bls12_381" else 4
+    return 6 if curve in ("bls12_381", "bls12_377") else 4
+
+
+def ref(curve):
+    """The Python reference that knows `curve`: oracle/pyref.py for its three curves; for BLS12-377 the private copy of it that
+    tests/harness/ref377.py extends (the module imported as `pyref` keeps three curves)."""
+    if curve != "bls12_377":
+        return pyref
+    from harness import ref377
+    return ref377.R
+
+
+def _field(name):
+    return (pyref.FIELDS.get(name) or ref("bls12_377").FIELDS[name])
 
 
 # ---- int <-> limb arrays -----------------------------------------------------------------
@@ -66,34 +79,34 @@ def limbs_to_ints(arr):
 
 
 def mont_R(field):
-    return 1 << (64 * pyref.FIELDS[field]["limbs64"])
+    return 1 << (64 * _field(field)["limbs64"])
 
 
 def to_mont_ints(field, vals):
-    p = pyref.FIELDS[field]["p"]
+    p = _field(field)["p"]
     R = mont_R(field)
     return [v * R % p for v in vals]
 
 
 def from_mont_ints(field, vals):
-    p = pyref.FIELDS[field]["p"]
+    p = _field(field)["p"]
     Ri = pow(mont_R(field), -1, p)
     return [v * Ri % p for v in vals]
 
 
 def fr_mont_array(curve, vals):
-    f = pyref.CURVES[curve]["fr"]
+    f = ref(curve).CURVES[curve]["fr"]
     return ints_to_limbs(to_mont_ints(f, vals), 4)
 
 
 def fr_from_mont_array(curve, arr):
-    f = pyref.CURVES[curve]["fr"]
+    f = ref(curve).CURVES[curve]["fr"]
     return from_mont_ints(f, limbs_to_ints(arr.reshape(-1, 4)))
 
 
 def points_to_array(curve, pts):
     """list of affine int points (or None) -> (n, 2*N) uint64 Montgomery array."""
-    f = pyref.CURVES[curve]["fq"]
+    f = ref(curve).CURVES[curve]["fq"]
     n64 = fq_limbs(curve)
     flat = []
     for P in pts:
@@ -104,7 +117,7 @@ def points_to_array(curve, pts):
 
 
 def array_to_points(curve, arr):
-    f = pyref.CURVES[curve]["fq"]
+    f = ref(curve).CURVES[curve]["fq"]
     n64 = fq_limbs(curve)
     arr = np.asarray(arr, dtype=np.uint64).reshape(-1, 2 * n64)
     vals = from_mont_ints(f, limbs_to_ints(arr.reshape(-1, n64)))

@@ -1,15 +1,17 @@
 """BLS12-377 through the C ABI on the device: G1 MSM, KZG commit / open on a true SRS, serialization, the Fr kernels (NTT, column
 digests, Ligero commit) and the group entry points -- every comparison bit for bit.
 
-The C++ oracle does not know the curve; the checker is the private copy of the Python reference (tests/harness/ref377.py).  MSM
-bases are P_i = (i + 1) G wherever possible, so that sum k_i P_i = (sum k_i (i + 1) mod r) G is ONE Python scalar multiplication;
-keys with other points carry their discrete logarithms along.  At n <= 64 the copy's naive `msm` is compared as well."""
+Two checkers that share nothing with the HIP code, and must agree with the device and so with each other: the private copy of the
+Python reference (tests/harness/ref377.py) and the C++ oracle (curve id 3; tests/test_oracle_bls12_377_cpu.py holds it against the
+copy on its own).  MSM bases are P_i = (i + 1) G wherever possible, so that sum k_i P_i = (sum k_i (i + 1) mod r) G is ONE Python
+scalar multiplication; keys with other points carry their discrete logarithms along.  At n <= 64 the copy's naive `msm` is compared
+as well.  The larger shapes of the curve run against the oracle in the files of the paths themselves (tests/test_msm_gpu.py, ...)."""
 import hashlib
-import random
 
 import numpy as np
 import pytest
 
+import oracle_lib as O
 from harness import ref377 as B
 
 pytestmark = pytest.mark.gpu
@@ -59,6 +61,7 @@ def test_msm_parity(ctx, key, form):
         if n <= 64:
             assert (want == B.point(R.msm(CURVE, pts[:n], ks))).all()
         canon, mont = B.fr(ks), B.fr_mont(ks)
+        assert (O.msm_pippenger(CURVE, words[:n], canon, 8, 1) == want).all() and (O.f_to_mont(CURVE, 1, canon) == mont).all(), n
         dc, dm = _dev(canon), _dev(mont)
         for sc, m in ((canon, False), (mont, True), (dc, False), (dm, True)):
             for rep in range(3 if sc is dc else 1):                                    # a repeated device call is captured, then replayed
@@ -69,7 +72,7 @@ def test_msm_parity(ctx, key, form):
     # a slice of the key (KZG10::commit skips leading zeros by offsetting the powers), and more scalars than bases left
     ks = R.gen_scalars(FR, 0x377100, 1000)
     got, _ = srs.msm(B.fr(ks), base_offset=1234)
-    assert (got == B.point(B.closed_form(ks, first=1235))).all()
+    assert (got == B.point(B.closed_form(ks, first=1235))).all() and (got == O.msm_pippenger(CURVE, np.ascontiguousarray(words[1234:]), B.fr(ks), 8, 1)).all()
     got, _ = srs.msm(B.fr(ks), base_offset=NMAX - 600)
     assert (got == B.point(B.closed_form(ks[:600], first=NMAX - 599))).all()
     job = srs.msm_async(B.fr(ks), base_offset=7)
@@ -77,40 +80,17 @@ def test_msm_parity(ctx, key, form):
     assert (got == B.point(B.closed_form(ks, first=8))).all() and not inf
 
 
-def _edge_keys(n):
-    """(name, discrete logarithms) of the keys of the edge sets; d = 0 is the (0, 0) infinity base, d < 0 a negated point"""
-    plain = [i + 1 for i in range(n)]
-    with_inf = list(plain)
-    with_inf[7] = 0
-    with_inf[min(100, n - 1)] = with_inf[min(100, n - 1) - 1]                        # a repeated base beside its copy
-    same = [7] * n                                                                     # P + P in every bucket that holds two entries
-    pairs = [(i // 2 + 1) * (1 if i % 2 == 0 else -1) for i in range(n)]               # P beside -P
-    return {"plain": plain, "infinity and a repeated base": with_inf, "one base": same, "P beside -P": pairs}
-
-
-def _edge_scalars(n, seed):
-    rnd = random.Random(seed)
-    one = rnd.randrange(r)
-    pair_vals = [rnd.randrange(r) for _ in range((n + 1) // 2)]
-    return {
-        "zeros": [0] * n, "ones": [1] * n, "r-1": [r - 1] * n, "alternating 0 and r-1": [0 if i % 2 == 0 else r - 1 for i in range(n)],
-        "one scalar repeated": [one] * n,                                               # one bucket per window spans every chunk
-        "equal in pairs": [pair_vals[i // 2] for i in range(n)],                       # with P beside -P: everything but the last cancels
-        "top window only": [((i % 0x12) + 1) << 248 for i in range(n)],
-        "just below r": [r - 1 - (i << 200) for i in range(n)],                        # the signed digits' carry out of the top window
-        "random": [rnd.randrange(r) for _ in range(n)],
-    }
-
-
 @pytest.mark.parametrize("n", [257, 4097])
 def test_msm_edge_sets(ctx, n):
     pts, _ = B.gen_bases(NMAX)
     by_dlog = lambda d: None if d == 0 else (pts[d - 1] if d > 0 else R.ec_neg(CURVE, pts[-d - 1]))
-    scalars = _edge_scalars(n, 0xED6E + n)
+    scalars = B.edge_scalars(n, 0xED6E + n)
     packed = {name: B.fr(ks) for name, ks in scalars.items()}
-    for kname, dl in _edge_keys(n).items():
+    for kname, dl in B.edge_keys(n).items():
         words = B.points([by_dlog(d) for d in dl])
         want = {name: _want(dl, ks) for name, ks in scalars.items()}
+        for name, sc in packed.items():
+            assert (O.msm_pippenger(CURVE, words, sc, 8, 2) == want[name]).all(), (n, kname, name)
         if kname == "P beside -P":                                                      # n is odd: the last point has no partner
             last = B.point(B.mul_g(scalars["equal in pairs"][-1] * dl[-1]))
             assert (want["equal in pairs"] == last).all()
@@ -123,9 +103,9 @@ def test_msm_edge_sets(ctx, n):
                 assert (got == want[name]).all() and inf == (not want[name].any()), (n, kname, form, name)
             srs.free()
     # the whole sum cancels: an even number of P, -P pairs with equal scalars
-    dl = _edge_keys(n - 1)["P beside -P"]
+    dl = B.edge_keys(n - 1)["P beside -P"]
     srs = ctx.upload_srs(CURVE, B.points([by_dlog(d) for d in dl]))
-    got, inf = srs.msm(B.fr(_edge_scalars(n - 1, 5)["equal in pairs"]))
+    got, inf = srs.msm(B.fr(B.edge_scalars(n - 1, 5)["equal in pairs"]))
     assert inf and not got.any()
     srs.free()
 
@@ -135,6 +115,7 @@ def test_msm_batch_and_many(ctx, key):
     pts, words, keys = key
     polys = [R.gen_scalars(FR, 0x377200 + j, 300) for j in range(3)]
     want = [B.point(B.closed_form(q)) for q in polys]
+    assert all((O.msm_pippenger(CURVE, words, B.fr(q), 8, 1) == w).all() for q, w in zip(polys, want))
     host = [B.fr_mont(q) for q in polys]
     dev = [_dev(h) for h in host]
     for form, srs in keys.items():
@@ -152,6 +133,7 @@ def test_msm_batch_and_many(ctx, key):
         arr = np.stack([B.fr_mont(q) for q in rows]) if montgomery else sc
         got, inf = keys["plain"].msm_many(arr, montgomery=montgomery)
         assert all((got[j] == B.point(B.closed_form(rows[j]))).all() for j in range(5)) and list(inf) == [False, False, False, True, False]
+        assert all((got[j] == O.msm_pippenger(CURVE, words, sc[j], 4, 1)).all() for j in range(5))
     got, _ = keys["plain"].msm_many(sc, base_offset=100)
     assert all((got[j] == B.point(B.closed_form(rows[j], first=101))).all() for j in range(5))
 
@@ -214,6 +196,9 @@ def test_kzg_commit_open(ctx, true_srs, degree):
     q, want_w, want_v = _open_expected(coeffs, z, beta)
     comm, _ = srs.msm(mont, montgomery=True)
     assert (comm == B.point(B.mul_g(R.poly_eval(FR, coeffs, beta)))).all()
+    powers = srs.read(0, n)
+    assert (O.kzg_commit(CURVE, powers, mont)[1] == comm).all() and (O.kzg_open(CURVE, powers, mont, zm)[1] == want_w).all()
+    assert (O.witness_poly(CURVE, mont, zm) == ctx.witness_poly(CURVE, mont, zm)).all() and B.fr_from_mont(O.poly_eval(CURVE, mont, zm)) == [want_v]
     for src in (mont, _dev(mont)):
         proof, inf = srs.kzg_open(src, zm, n=n)
         assert (proof == want_w).all() and not inf
@@ -240,6 +225,8 @@ def test_kzg_leading_zeros_and_lincomb(ctx, true_srs):
     assert (srs.msm(B.fr_mont(coeffs), montgomery=True)[0] == want_c).all()
     _, want_w, want_v = _open_expected(coeffs, z, beta)
     assert (srs.kzg_open(B.fr_mont(coeffs), zm)[0] == want_w).all()
+    powers = srs.read(0, 300)
+    assert (O.kzg_commit(CURVE, powers, B.fr_mont(coeffs))[1] == want_c).all() and (O.kzg_open(CURVE, powers, B.fr_mont(coeffs), zm)[1] == want_w).all()
     assert B.fr_from_mont(ctx.poly_eval(CURVE, B.fr_mont(coeffs), zm)) == [want_v]
     # Marlin's open: p = sum_j xi_j p_j on the device (marlin_pc/mod.rs:281-287), then the opening of p
     import torch
@@ -277,6 +264,8 @@ def test_serialization(ctx, compressed):
     assert len(data) == 8 + 9 * (48 if compressed else 96)
     srs = ctx.upload_srs(CURVE, words)
     assert srs.serialize(compressed=compressed) == data
+    if not compressed:
+        assert data[8:] == b"".join(O.ser_point(CURVE, w) for w in words)
     assert srs.serialize(offset=2, count=3, compressed=compressed) == R.ser_g1_vec(CURVE, pts[2:5], compressed)
     srs.free()
     loaded, used = ctx.load_serialized_srs(CURVE, data + b"the fields behind powers_of_g", compressed)
@@ -326,7 +315,7 @@ def test_ntt(ctx, log_n, in_cols):
     co = [R.gen_scalars(FR, 0x377500 + 16 * log_n + j, in_cols) for j in range(rows)]
     mont = np.stack([B.fr_mont(c) for c in co])
     got = ctx.ntt_batch(CURVE, mont, log_n)
-    assert got.shape == (rows, 1 << log_n, 4)
+    assert got.shape == (rows, 1 << log_n, 4) and (got == O.ntt_batch(CURVE, mont, log_n)).all()
     for j in range(rows):
         assert B.fr_from_mont(got[j]) == R.ntt(FR, co[j], log_n), (log_n, j)
     if log_n == 5:            # the reference's own statement (linear_codes/utils.rs:303-331): encoded[j] = p(omega^j)

@@ -5,16 +5,20 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-import pyref as R
 
 pytestmark = pytest.mark.gpu
-CURVES = ["bls12_381", "bn254", "pallas"]
+CURVES = ["bls12_381", "bn254", "pallas", "bls12_377"]
+
+
+def _fr_modulus(curve):
+    ref = O.ref(curve)
+    return ref.FIELDS[ref.CURVES[curve]["fr"]]["p"]
 
 
 @pytest.mark.parametrize("curve", CURVES)
 def test_glv_table_msm_sizes_and_edge_scalars(ctx, curve):
     nmax = 4200
-    r = R.FIELDS[R.CURVES[curve]["fr"]]["p"]
+    r = _fr_modulus(curve)
     bases = O.gen_bases(curve, nmax)
     bases[7] = 0
     bases[100] = bases[99]
@@ -48,7 +52,7 @@ def test_glv_table_msm_sizes_and_edge_scalars(ctx, curve):
     srs.free()
 
 
-@pytest.mark.parametrize("curve", ["bls12_381", "bn254"])
+@pytest.mark.parametrize("curve", ["bls12_381", "bn254", "bls12_377"])
 def test_glv_table_kzg_commit_open_and_batch(ctx, curve):
     import torch
     n = (1 << 15) + 1
@@ -79,7 +83,7 @@ def test_glv_table_randomised_against_the_full_table(ctx):
         keys = [ctx.upload_srs(curve, bases) for _ in range(3)]
         keys[1].precompute(min_pairs=1, glv=False)
         keys[2].precompute(min_pairs=1, glv=True)
-        r = R.FIELDS[R.CURVES[curve]["fr"]]["p"]
+        r = _fr_modulus(curve)
         for _ in range(12):
             n = rnd.randrange(1, nmax + 1)
             kind = rnd.randrange(4)

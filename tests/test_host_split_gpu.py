@@ -18,7 +18,7 @@ import numpy as np, torch
 import oracle_lib as O
 import poly_commit_amd as pc
 ctx = pc.Context(0)
-for curve in ("bls12_381", "bn254", "pallas"):
+for curve in ("bls12_381", "bn254", "pallas", "bls12_377"):
     nmax = 5000
     powers = O.gen_bases(curve, nmax)
     srs = ctx.upload_srs(curve, powers)

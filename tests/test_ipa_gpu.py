@@ -159,7 +159,7 @@ def test_ipa_rounds_randomised_differential():
     the generators, zero coefficients -- whole openings against the oracle (1343 openings with 209 two-level and 280 one-level table
     folds in 240 s without a mismatch on the round-6 library)."""
     import subprocess, sys
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ipa_fuzz.py"), "15", "20260930"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "ipa_fuzz.py"), "15", "20260930", "--curves", "bls12_381,bn254,pallas"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "0 mismatches" in r.stdout
 

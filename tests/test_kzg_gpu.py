@@ -11,7 +11,7 @@ import oracle_lib as O
 import pyref as R
 
 pytestmark = pytest.mark.gpu
-CURVES = ["bls12_381", "bn254", "pallas"]
+CURVES = ["bls12_381", "bn254", "pallas", "bls12_377"]
 
 
 @pytest.mark.parametrize("curve", CURVES)
@@ -74,15 +74,16 @@ def test_witness_identity(ctx):
 
 
 def _int_fr(curve):
-    return R.FIELDS[R.CURVES[curve]["fr"]]["p"]
+    ref = O.ref(curve)
+    return ref.FIELDS[ref.CURVES[curve]["fr"]]["p"]
 
 
-@pytest.mark.parametrize("curve,d", [("bls12_381", 1 << 16), ("bn254", 1 << 14)])
+@pytest.mark.parametrize("curve,d", [("bls12_381", 1 << 16), ("bn254", 1 << 14), ("bls12_377", 1 << 14)])
 def test_true_srs_end_to_end_trapdoor_check(ctx, curve, d):
     """end_to_end_test (kzg10/mod.rs:546-575) at scale with a TRUE SRS built on the GPU
     (KZG10::setup's g.batch_mul(powers_of_beta), :68-76): commit and open on the GPU, then the
     verifier's pairing equation e(C - v g, h) = e(W, beta h - z h) (:314-333) is checked in G1
-    with the known trapdoor:  C - v*g == (beta - z) * W."""
+    with the known trapdoor:  C - v*g == (beta - z) * W.  The oracle's kzg_commit / kzg_open over the same powers give the same two points."""
     import torch
     import poly_commit_amd as pc
     p = _int_fr(curve)
@@ -114,6 +115,9 @@ def test_true_srs_end_to_end_trapdoor_check(ctx, curve, d):
     lhs = pc.points_sum(curve, np.stack([comm, pc.point_mul(curve, g, neg_v)]))
     rhs = pc.point_mul(curve, w, O.fr_mont_array(curve, [(b - zi) % p])[0])
     assert (lhs == rhs).all() and lhs.any()
+    powers = srs.read(0, n)
+    assert (comm == O.kzg_commit(curve, powers, coeffs, 16)[1]).all() and (w == O.kzg_open(curve, powers, coeffs, z_m, 16)[1]).all()
+    assert (srs.kzg_open(coeffs, z_m)[0] == w).all()
     srs.free()
 
 
@@ -189,12 +193,13 @@ def test_sharded_engine_world1_matches_oracle(ctx):
     eng.srs.free()
 
 
-@pytest.mark.parametrize("curve", ["bls12_381", "bn254", "pallas"])
+@pytest.mark.parametrize("curve", CURVES)
 def test_fr_lincomb_matches_bigint(ctx, curve):
     """MarlinKZG10::open's p = sum_j xi_j p_j (marlin_pc/mod.rs:281-287), ragged lengths, host and
     device-resident inputs; followed by the witness division it feeds (:307-312)."""
     import torch
     lens = [1000, 1, 517, 1000, 64, 0]
+    R = O.ref(curve)
     polys_i = [R.gen_scalars(curve + "_fr", 0x5EED0700 + j, n) for j, n in enumerate(lens)]
     xi_i = R.gen_scalars(curve + "_fr", 0x5EED0777, len(lens))
     want = R.fr_lincomb(curve + "_fr", polys_i, xi_i)
@@ -219,7 +224,7 @@ ROW_MUL_V = [12, 41, 55]
 ROW_MUL_WANT = [4088, 4431, 543]
 
 
-@pytest.mark.parametrize("curve", ["bls12_381", "bn254", "pallas"])
+@pytest.mark.parametrize("curve", CURVES)
 def test_row_mul_reference_vector(ctx, curve):
     """`mat.row_mul(&v) == [4088, 4431, 543]` (utils.rs:274-286) through pc_hip_fr_lincomb, the entry point
     that replaces row_mul; given in the integers, so it holds in every scalar field."""
@@ -228,7 +233,7 @@ def test_row_mul_reference_vector(ctx, curve):
     assert O.fr_from_mont_array(curve, got) == ROW_MUL_WANT
 
 
-@pytest.mark.parametrize("curve", ["bls12_381", "bn254", "pallas"])
+@pytest.mark.parametrize("curve", CURVES)
 def test_poly_eval_matches_oracle(ctx, curve):
     """pc_hip_poly_eval (the up-sweep of the division scan alone) == Horner evaluation of the oracle,
     host and device-resident coefficients, lengths around the chunk sizes of the scan levels."""
@@ -285,11 +290,12 @@ def test_golden_ligero_commit_lincomb_msm_many(ctx):
 
 
 @pytest.mark.parametrize("curve,compressed", [("bls12_381", True), ("bls12_381", False), ("bn254", True), ("bn254", False), ("pallas", False),
-                                              ("pallas", True)])
+                                              ("pallas", True), ("bls12_377", True), ("bls12_377", False)])
 def test_srs_from_ark_serialize_bytes(ctx, curve, compressed):
     """pc_hip_srs_load_serialized: the head of a serialized kzg10::UniversalParams (Vec<G1Affine>: u64 length + points,
     kzg10/data_structures.rs:57-112) decoded on the device into a resident SRS; a commitment over it equals the oracle's."""
     import poly_commit_amd as pc
+    R = O.ref(curve)
     n = 300
     pts = R.gen_bases(curve, n)
     pts[7] = R.ec_neg(curve, pts[7])
@@ -303,6 +309,12 @@ def test_srs_from_ark_serialize_bytes(ctx, curve, compressed):
     # the writer: the resident points back to exactly the bytes CanonicalSerialize wrote (pc_hip_srs_serialize), whole and in part
     assert srs.serialize(compressed=compressed) == R.ser_g1_vec(curve, pts, compressed)
     assert srs.serialize(5, 20, compressed=not compressed) == R.ser_g1_vec(curve, pts[5:25], not compressed)
+    # ... and the C++ oracle's bytes of the same points, written and read (the second checker of the uncompressed form)
+    theirs = n.to_bytes(8, "little") + b"".join(O.ser_point(curve, a) for a in arr)
+    assert srs.serialize(compressed=False) == theirs
+    srs.free()
+    srs, used3 = ctx.load_serialized_srs(curve, theirs, False)
+    assert used3 == len(theirs) and (srs.read(0, n) == arr).all()
     srs.free()
     # only the first 100 points (a committer key shorter than the ceremony)
     srs, used2 = ctx.load_serialized_srs(curve, data, compressed, max_points=100)
@@ -319,7 +331,8 @@ def test_srs_from_ark_serialize_bytes(ctx, curve, compressed):
 
 def test_srs_with_infinity_round_trips_through_the_writer(ctx):
     """Infinity in a key (flag 0x40, x = y = 0) survives load -> serialize in every encoding, Pallas compressed included."""
-    for curve in ("bls12_381", "bn254", "pallas"):
+    for curve in CURVES:
+        R = O.ref(curve)
         pts = R.gen_bases(curve, 9)
         pts[3] = None
         pts[6] = R.ec_neg(curve, pts[6])
@@ -327,4 +340,6 @@ def test_srs_with_infinity_round_trips_through_the_writer(ctx):
             data = R.ser_g1_vec(curve, pts, compressed)
             srs, used = ctx.load_serialized_srs(curve, data, compressed)
             assert used == len(data) and srs.serialize(compressed=compressed) == data
+            if not compressed:
+                assert data == (9).to_bytes(8, "little") + b"".join(O.ser_point(curve, a) for a in srs.read(0, 9))
             srs.free()

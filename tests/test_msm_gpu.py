@@ -11,7 +11,20 @@ import pyref as R
 
 pytestmark = pytest.mark.gpu
 
-CURVES = ["bls12_381", "bn254", "pallas"]
+CURVES = ["bls12_381", "bn254", "pallas", "bls12_377"]
+
+
+def _fr_modulus(curve):
+    ref = O.ref(curve)
+    return ref.FIELDS[ref.CURVES[curve]["fr"]]["p"]
+
+
+def _and_bls12_377(curve, cases):
+    """the cases on their curve under the ids they always had, then once more on BLS12-377: the one curve whose default build keeps
+    the accumulate's running sum in twelve 32-bit limbs (add_affine_lz and the lazily reduced store form; AccSum<C>, csrc/msm.hpp),
+    under a modulus that leaves that form less room (2^384 / p = 9.52 against BLS12-381's 9.84, LAZY_STORE_OK wants 9)"""
+    name = lambda c: "-".join(str(v) for v in c)
+    return [pytest.param(curve, *c, id=name(c)) for c in cases] + [pytest.param("bls12_377", *c, id="bls12_377-" + name(c)) for c in cases]
 
 
 def _check(srs, curve, bases, scalars, **kw):
@@ -36,7 +49,8 @@ def test_msm_small_sizes(ctx, curve):
 @pytest.mark.parametrize("curve", CURVES)
 def test_msm_edge_scalars(ctx, curve):
     n = 1500
-    r = R.FIELDS[R.CURVES[curve]["fr"]]["p"]
+    r = _fr_modulus(curve)
+    top = r.bit_length() - 1                                # 2^top <= r - 1 < 2^(top + 1): 254, 253 (BN254), 252 (BLS12-377)
     bases = O.gen_bases(curve, n)
     bases[7] = 0            # a point at infinity among the bases
     bases[100] = bases[99]  # repeated base
@@ -48,9 +62,8 @@ def test_msm_edge_scalars(ctx, curve):
         "r-1": O.ints_to_limbs([r - 1] * n, 4),
         "same": np.repeat(rnd[:1], n, axis=0),
         "half-zero": np.where((np.arange(n) % 2 == 0)[:, None], rnd, 0).astype(np.uint64),
-        "low-hamming": O.ints_to_limbs([1 << (i % 254) for i in range(n)], 4),
-        "window-carry": O.ints_to_limbs([(1 << 254) - 1 - (i << 60) for i in range(n)], 4) if curve != "bn254" else
-                        O.ints_to_limbs([(1 << 253) - 1 - (i << 60) for i in range(n)], 4),
+        "low-hamming": O.ints_to_limbs([1 << (i % min(254, top + 1)) for i in range(n)], 4),
+        "window-carry": O.ints_to_limbs([(1 << top) - 1 - (i << 60) for i in range(n)], 4),
     }
     for name, sc in cases.items():
         sc = np.ascontiguousarray(sc)
@@ -86,9 +99,8 @@ def test_msm_offset_truncation_montgomery(ctx, curve):
     srs.free()
 
 
-@pytest.mark.parametrize("c,T", [(4, 1), (7, 3), (10, 16), (13, 64), (16, 0)])
-def test_msm_tunings(ctx, c, T):
-    curve = "bls12_381"
+@pytest.mark.parametrize("curve,c,T", _and_bls12_377("bls12_381", [(4, 1), (7, 3), (10, 16), (13, 64), (16, 0)]))
+def test_msm_tunings(ctx, curve, c, T):
     n = 5000
     bases = O.gen_bases(curve, n)
     scalars = O.gen_scalars(curve, 1234, n)
@@ -101,13 +113,12 @@ def test_msm_tunings(ctx, c, T):
         ctx.set_msm_tuning(0, 0)
 
 
-@pytest.mark.parametrize("T", [1, 2, 5, 8])
-@pytest.mark.parametrize("n,table", [(700, False), (5000, True), (40000, False), (70001, True)])
-def test_msm_chains_of_cut_buckets(ctx, T, n, table):
+@pytest.mark.parametrize("curve,n,table,T", _and_bls12_377("bls12_381", [(n, table, T) for n, table in ((700, False), (5000, True), (40000, False), (70001, True))
+                                                                        for T in (1, 2, 5, 8)]))
+def test_msm_chains_of_cut_buckets(ctx, curve, T, n, table):
     """The joins of buckets that chunk edges cut (k_accumulate's in-workgroup scan, k_accumulate_edges, the segmented reduction
     behind them): small chunks against distributions whose buckets span a few lanes, a whole workgroup, several workgroups --
     uniform, a handful of values, all equal, mostly zero -- with and without the window table; bit-identical to the oracle."""
-    curve = "bls12_381"
     bases = O.gen_bases(curve, n)
     rnd = O.gen_scalars(curve, 0xC4A1 + n, n)
     idx = np.arange(n)
@@ -125,7 +136,7 @@ def test_msm_chains_of_cut_buckets(ctx, T, n, table):
             srs.precompute()
         for name, sc in dists.items():
             got, _ = srs.msm(sc)
-            assert (got == O.msm_pippenger(curve, bases, sc, 8, 1)).all(), (name, T, n, table)
+            assert (got == O.msm_pippenger(curve, bases, sc, 8, 1)).all(), (curve, name, T, n, table)
         srs.free()
     finally:
         ctx.set_msm_tuning(0, 0)
@@ -147,14 +158,21 @@ def test_msm_linearity(ctx):
     srs.free()
 
 
-def test_msm_2_16_bls(ctx):
-    curve = "bls12_381"
+def _msm_2_16(ctx, curve):
     n = (1 << 16) + 1
     bases = O.gen_bases(curve, n)
     scalars = O.gen_scalars(curve, 0x5EED0001, n)
     srs = ctx.upload_srs(curve, bases)
     _check(srs, curve, bases, scalars)
     srs.free()
+
+
+def test_msm_2_16_bls(ctx):
+    _msm_2_16(ctx, "bls12_381")
+
+
+def test_msm_2_16_bls12_377(ctx):
+    _msm_2_16(ctx, "bls12_377")
 
 
 def test_msm_async_pipeline_and_batch(ctx):
@@ -294,7 +312,7 @@ def test_msm_window_table_small(ctx, curve):
     want = O.msm_pippenger(curve, bases, s, 8, 1)
     srs = ctx.upload_srs(curve, bases)
     assert (srs.msm(s)[0] == want).all()
-    r = R.FIELDS[curve + "_fr"]["p"]
+    r = _fr_modulus(curve)
     top = O.ints_to_limbs([r - 1] * n, 4)
     for c in (0, 5, 9, 12, 16):
         srs.precompute(window_bits=c, min_pairs=1)
@@ -358,7 +376,7 @@ def test_msm_many_small(ctx, curve):
     s = O.gen_scalars(curve, 0x4A11, B * m).reshape(B, m, 4)
     s[5] = 0
     s[6, :, :] = s[6, :1, :]
-    r = R.FIELDS[curve + "_fr"]["p"]
+    r = _fr_modulus(curve)
     s[7] = O.ints_to_limbs([r - 1] * m, 4)
     s = np.ascontiguousarray(s)
     for off in (0, 50):
@@ -458,14 +476,14 @@ def test_msm_batch_fast_path_over_window_table(ctx, curve, k):
     srs.free()
 
 
-def test_msm_repeated_call_through_captured_graph(monkeypatch):
+def _repeated_call_through_captured_graph(monkeypatch, curve):
     """PC_HIP_GRAPHS=1: the second identical call (same resident bases, same device scalar buffer) is captured into a
     hipGraph, later ones replay it; a different buffer in between takes another slot.  Every result equals the oracle's."""
     import torch
     import poly_commit_amd as pc
     monkeypatch.setenv("PC_HIP_GRAPHS", "1")
     ctx = pc.Context(0)
-    curve, n = "bls12_381", 5000
+    n = 5000
     bases = O.gen_bases(curve, n)
     sc = [O.gen_scalars(curve, 0x6A0 + k, n) for k in range(2)]
     want = [O.msm_pippenger(curve, bases, s, 8, 1) for s in sc]
@@ -484,7 +502,15 @@ def test_msm_repeated_call_through_captured_graph(monkeypatch):
     ctx.close()
 
 
-def test_msm_graph_replay_survives_a_growing_scratch_buffer():
+def test_msm_repeated_call_through_captured_graph(monkeypatch):
+    _repeated_call_through_captured_graph(monkeypatch, "bls12_381")
+
+
+def test_msm_repeated_call_through_captured_graph_bls12_377(monkeypatch):
+    _repeated_call_through_captured_graph(monkeypatch, "bls12_377")
+
+
+def _graph_replay_survives_a_growing_scratch_buffer(curve):
     """Calls of at most 2^18 pairs on device scalars replay a captured hipGraph from their third occurrence on (the library's default).
     A captured graph holds the addresses of the pipeline's grow-only scratch as they were; a LARGER call on the same pipeline then
     reallocates that scratch.  Round 6: the replay after it read freed memory (a GPU memory access fault in the second IPA opening of
@@ -493,7 +519,7 @@ def test_msm_graph_replay_survives_a_growing_scratch_buffer():
     import torch
     import poly_commit_amd as pc
     ctx = pc.Context(0)
-    curve, n_small, n_big = "pallas", 3000, 1 << 16
+    n_small, n_big = 3000, 1 << 16
     bases = O.gen_bases(curve, n_big)
     sc_small, sc_big = O.gen_scalars(curve, 0x6B0, n_small), O.gen_scalars(curve, 0x6B1, n_big)
     want_small = O.msm_pippenger(curve, np.ascontiguousarray(bases[:n_small]), sc_small, 8, 1)
@@ -513,32 +539,54 @@ def test_msm_graph_replay_survives_a_growing_scratch_buffer():
     ctx.close()
 
 
+def test_msm_graph_replay_survives_a_growing_scratch_buffer():
+    _graph_replay_survives_a_growing_scratch_buffer("pallas")
+
+
+def test_msm_graph_replay_survives_a_growing_scratch_buffer_bls12_377():
+    _graph_replay_survives_a_growing_scratch_buffer("bls12_377")
+
+
+THREE = "bls12_381,bn254,pallas"
+
+
+def _fuzz(tool, seconds, seed, curves):
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", tool), seconds, seed, "--curves", curves], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "0 mismatches" in r.stdout
+
+
 def test_msm_graph_path_randomised_differential():
     """tools/graph_fuzz.py for a few seconds: resident buffers and call shapes repeated in random order on one key (plain, captured,
     replayed on every pipeline), with growing scratch, pc_hip_ctx_trim, table builds and in-place key folds in between (21 442 cases with
     11 176 repeats in 150 s without a mismatch on the round-6 library)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "graph_fuzz.py"), "12", "20260930"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "0 mismatches" in r.stdout
+    _fuzz("graph_fuzz.py", "12", "20260930", THREE)
+
+
+def test_msm_graph_path_randomised_differential_bls12_377():
+    """the same slice on BLS12-377 alone"""
+    _fuzz("graph_fuzz.py", "12", "20260930", "bls12_377")
 
 
 def test_msm_randomised_differential():
-    """tools/msm_fuzz.py for a few seconds: random sizes / chunk lengths / window widths / tables / scalar distributions on all three
+    """tools/msm_fuzz.py for a few seconds: random sizes / chunk lengths / window widths / tables / scalar distributions on the first three
     curves against the oracle (6000 cases in 150 s without a mismatch on the round-3 library; this keeps ~400 of them in the suite)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "msm_fuzz.py"), "10", "20260926"], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "0 mismatches" in r.stdout
+    _fuzz("msm_fuzz.py", "10", "20260926", THREE)
 
 
-@pytest.mark.parametrize("curve", ["bls12_381", "bn254"])
+def test_msm_randomised_differential_bls12_377():
+    """the same slice on BLS12-377 alone: the 12-limb lazily reduced accumulate under every chunk length, window width and distribution"""
+    _fuzz("msm_fuzz.py", "10", "20260926", "bls12_377")
+
+
+@pytest.mark.parametrize("curve", ["bls12_381", "bn254", "bls12_377"])
 def test_msm_equal_partial_sums_meet_in_the_joins(ctx, curve):
     """ONE base under ONE scalar: every chunk of a bucket's run sums to the same point, so the in-workgroup scan of k_accumulate, the
     edge kernel, the segmented and the (two-lane) bucket reduction all add EQUAL partial sums -- XyzzD::add / the two-lane half_add take
-    their doubling branch on coordinates that left the accumulation lazily reduced (BLS12-381) or canonical (BN254).  Round-3 advisor
+    their doubling branch on coordinates that left the accumulation lazily reduced (BLS12-381 in radix 2^30, BLS12-377 in twelve 32-bit
+    limbs) or canonical (BN254).  Round-3 advisor
     finding; tests/test_emu_cpu.py steps the same shape on the CPU."""
     g = O.gen_bases(curve, 3)
     for n, chunk in ((64, 0), (4096, 0), (4096, 2), (5000, 5), (1 << 15, 0)):

@@ -10,12 +10,13 @@ import oracle_lib as O
 import pyref as R
 
 pytestmark = pytest.mark.gpu
-CURVES = ["bls12_381", "bn254", "pallas"]
+CURVES = ["bls12_381", "bn254", "pallas", "bls12_377"]
 
 
 @pytest.mark.parametrize("curve", CURVES)
 def test_reed_solomon_small(ctx, curve):
     """sizes 2^1..2^9, rho_inv = 3 -> domain = next_pow2(3 m), as in the reference test."""
+    R = O.ref(curve)
     fr = R.CURVES[curve]["fr"]
     for i in range(1, 10):
         m = 1 << i
@@ -190,13 +191,13 @@ def test_ligero_commit_fused_vs_restatement(ctx, curve):
 
 @pytest.mark.parametrize("curve,log_n,in_cols", [("bls12_381", 18, 1 << 16), ("bls12_381", 18, 50000), ("pallas", 18, (1 << 18) - 3),
                                                  ("bn254", 20, 1 << 18), ("bls12_381", 20, 300001), ("bls12_381", 22, 1 << 20),
-                                                 ("pallas", 22, (1 << 21) + 12345), ("bn254", 22, 1 << 22)])
+                                                 ("pallas", 22, (1 << 21) + 12345), ("bn254", 22, 1 << 22), ("bls12_377", 18, 50000)])
 def test_ntt_large_sizes_dynamic_lds(ctx, curve, log_n, in_cols):
     """log_n 18 .. PC_HIP_NTT_MAX_LOG_N = 22: one factor of the four-step split reaches 2^11, the tile (plus the stage twiddles)
     needs more than the 64 KiB default of dynamic LDS (ntt.hpp: hipFuncAttributeMaxDynamicSharedMemorySize), and the zero-skip
     covers ragged in_cols.  Whole rows against the oracle's NTT, test_reed_solomon's property (linear_codes/utils.rs:303-331) at a
     few j, and the DC term."""
-    fr = R.FIELDS[R.CURVES[curve]["fr"]]["p"]
+    fr = O.ref(curve).FIELDS[O.ref(curve).CURVES[curve]["fr"]]["p"]
     rows = 2 if log_n < 22 else 1
     co = O.gen_scalars(curve, 0x22 + log_n + in_cols, rows * in_cols)
     mont = O.f_to_mont(curve, 1, co).reshape(rows, in_cols, 4)
@@ -210,11 +211,21 @@ def test_ntt_large_sizes_dynamic_lds(ctx, curve, log_n, in_cols):
     assert O.fr_from_mont_array(curve, got[0, :1])[0] == sum(O.limbs_to_ints(co[:in_cols])) % fr
 
 
-def test_field_kernels_randomised_differential():
-    """tools/field_fuzz.py for a few seconds: the division scan (with carries and chained pieces), the batched NTT (ragged shapes,
-    the Horner property) and the fused IPA fold + inner products against the oracle / Python big ints on all three fields."""
+def _field_fuzz(curves):
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "tools", "field_fuzz.py"), "12", "20260927"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, os.path.join(root, "tools", "field_fuzz.py"), "12", "20260927", "--curves", curves], capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "0 mismatches" in r.stdout
+
+
+def test_field_kernels_randomised_differential():
+    """tools/field_fuzz.py for a few seconds: the division scan (with carries and chained pieces), the batched NTT (ragged shapes,
+    the Horner property) and the fused IPA fold + inner products against the oracle / Python big ints on the first three fields."""
+    _field_fuzz("bls12_381,bn254,pallas")
+
+
+def test_field_kernels_randomised_differential_bls12_377():
+    """the same slice on BLS12-377's Fr alone (two-adicity 47, a 253-bit modulus)"""
+    _field_fuzz("bls12_377")

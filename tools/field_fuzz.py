@@ -5,7 +5,7 @@
          whole output against the oracle's NTT and test_reed_solomon's property out[j] == row(omega^j) at random j, utils.rs:303-331)
   fold   pc_hip_ipa_fold_dots (ipa_pc/mod.rs:672,675,691-697; random power-of-two m, with and without the fold; folded vectors
          and both inner products against Python big ints)
-`python tools/field_fuzz.py [seconds] [seed] [kinds]`.  One line per failure and a summary; exit code 1 on any mismatch."""
+`python tools/field_fuzz.py [seconds] [seed] [kinds] [--curves a,b]` (every curve of the oracle, four of them, unless told otherwise).  One line per failure and a summary; exit code 1 on any mismatch."""
 import os, sys, time, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
@@ -15,17 +15,25 @@ import torch
 import oracle_lib as O
 import poly_commit_amd as pc
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-kinds = sys.argv[3].split(",") if len(sys.argv) > 3 else ["div", "ntt", "fold"]
-CURVES = ("bls12_381", "bn254", "pallas")
+ALL_CURVES = tuple(O.CURVES)                                # every curve the oracle knows: the fuzzers have no other checker
+argv = sys.argv[1:]
+CURVES = ALL_CURVES
+if "--curves" in argv:
+    i = argv.index("--curves")
+    CURVES = tuple(argv[i + 1].split(","))
+    del argv[i:i + 2]
+assert CURVES and all(c in ALL_CURVES for c in CURVES), CURVES
+budget = float(argv[0]) if len(argv) > 0 else 60.0
+rng = random.Random(int(argv[1]) if len(argv) > 1 else 1)
+kinds = argv[2].split(",") if len(argv) > 2 else ["div", "ntt", "fold"]
 ctx = pc.Context(0)
 MOD = {c: None for c in CURVES}
 
 
 def modulus(curve):
     if MOD[curve] is None:
-        import pyref as R
+        import pyref
+        R = pyref if curve in pyref.CURVES else O.ref(curve)    # the Python reference's own three curves, else the copy that has the fourth
         MOD[curve] = R.FIELDS[R.CURVES[curve]["fr"]]["p"]
     return MOD[curve]
 

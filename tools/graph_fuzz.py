@@ -2,7 +2,7 @@
 a few resident buffers and (length, offset) shapes called again and again in random order on one key per curve -- so that calls are run
 plain, captured and replayed on all three pipelines in every interleaving -- with larger calls that make a pipeline's scratch grow,
 pc_hip_ctx_trim, window-table builds and in-place key folds thrown in.  Every result against the CPU oracle.
-`python tools/graph_fuzz.py [seconds] [seed]`; exit code 1 on any mismatch."""
+`python tools/graph_fuzz.py [seconds] [seed] [--curves a,b]` (every curve of the oracle, four of them, unless told otherwise); exit code 1 on any mismatch."""
 import os, sys, time, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
@@ -12,13 +12,21 @@ import torch
 import oracle_lib as O
 import poly_commit_amd as pc
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+ALL_CURVES = tuple(O.CURVES)                                # every curve the oracle knows: the fuzzers have no other checker
+argv = sys.argv[1:]
+CURVES = ALL_CURVES
+if "--curves" in argv:
+    i = argv.index("--curves")
+    CURVES = tuple(argv[i + 1].split(","))
+    del argv[i:i + 2]
+assert CURVES and all(c in ALL_CURVES for c in CURVES), CURVES
+budget = float(argv[0]) if len(argv) > 0 else 60.0
+rng = random.Random(int(argv[1]) if len(argv) > 1 else 1)
 ctx = pc.Context(0)
 NMAX = 1 << 16
 t0, cases, bad, replays_possible = time.time(), 0, 0, 0
 while time.time() - t0 < budget:
-    curve = rng.choice(["bls12_381", "bn254", "pallas"])
+    curve = rng.choice(list(CURVES))
     n_key = rng.choice([1 << 10, 1 << 13, NMAX])
     bases = O.gen_bases(curve, n_key)
     host = [O.gen_scalars(curve, 0xF100 + k, n_key) for k in range(3)]

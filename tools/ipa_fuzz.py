@@ -1,6 +1,6 @@
 """Randomised differential test of the IPA halving rounds (poly_commit_amd/ipa.py over the C ABI) against the CPU oracle: random curve,
 size, fold-table form (none / one level / two levels, digit widths 2..5 or the library's choice), switch to the fixed key, resident or
-host key, points at infinity among the generators, zero coefficients.  `python tools/ipa_fuzz.py [seconds] [seed]`; exit 1 on a mismatch."""
+host key, points at infinity among the generators, zero coefficients.  `python tools/ipa_fuzz.py [seconds] [seed] [--curves a,b]` (every curve of the oracle, four of them, unless told otherwise); exit 1 on a mismatch."""
 import os, sys, time, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
@@ -11,14 +11,23 @@ import oracle_lib as O
 import poly_commit_amd as pc
 from poly_commit_amd import ipa
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+ALL_CURVES = tuple(O.CURVES)                                # every curve the oracle knows: the fuzzers have no other checker
+argv = sys.argv[1:]
+CURVES = ALL_CURVES
+if "--curves" in argv:
+    i = argv.index("--curves")
+    CURVES = tuple(argv[i + 1].split(","))
+    del argv[i:i + 2]
+assert CURVES and all(c in ALL_CURVES for c in CURVES), CURVES
+budget = float(argv[0]) if len(argv) > 0 else 60.0
+rng = random.Random(int(argv[1]) if len(argv) > 1 else 1)
+SIX_LIMBS = ("bls12_381", "bls12_377")                     # scalar multiplications over a 12-word Fq: smaller keys, no cached fixed key
 ctx = pc.Context(0)
 t0, cases, bad, kinds_seen = time.time(), 0, 0, {}
 while time.time() - t0 < budget:
-    curve = rng.choice(["pallas", "pallas", "bn254", "bls12_381"])
+    curve = rng.choice([c for c in ("pallas", "pallas", "bn254", "bls12_381", "bls12_377") if c in CURVES])      # Pallas, the IPA's own curve, twice
     lg = rng.randint(1, 11 if curve == "pallas" else 9)
-    big = curve != "bls12_381" and rng.random() < 0.06                 # now and then a size where the late rounds get the cached fixed key (n0 >= 2^12)
+    big = curve not in SIX_LIMBS and rng.random() < 0.06                 # now and then a size where the late rounds get the cached fixed key (n0 >= 2^12)
     if big:
         lg = rng.randint(12, 13)
     n = 1 << lg

@@ -1,6 +1,6 @@
 """Randomised differential test of pc_hip_msm against the CPU oracle: random sizes, chunk lengths, window widths (or the window
-table), scalar distributions whose buckets span from a fraction of a chunk to many workgroups.  `python tools/msm_fuzz.py [seconds] [seed]`.
-Prints one line per failure and a summary; exit code 1 on any mismatch."""
+table), scalar distributions whose buckets span from a fraction of a chunk to many workgroups.  `python tools/msm_fuzz.py [seconds] [seed] [--curves a,b]`
+(every curve of the oracle, four of them, unless told otherwise).  Prints one line per failure and a summary; exit code 1 on any mismatch."""
 import os, sys, time, random
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):
@@ -9,11 +9,19 @@ import numpy as np
 import oracle_lib as O
 import poly_commit_amd as pc
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
-rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+ALL_CURVES = tuple(O.CURVES)                                # every curve the oracle knows: the fuzzers have no other checker
+argv = sys.argv[1:]
+CURVES = ALL_CURVES
+if "--curves" in argv:
+    i = argv.index("--curves")
+    CURVES = tuple(argv[i + 1].split(","))
+    del argv[i:i + 2]
+assert CURVES and all(c in ALL_CURVES for c in CURVES), CURVES
+budget = float(argv[0]) if len(argv) > 0 else 60.0
+rng = random.Random(int(argv[1]) if len(argv) > 1 else 1)
 ctx = pc.Context(0)
 NMAX = 1 << 17
-bases = {c: O.gen_bases(c, NMAX) for c in ("bls12_381", "bn254", "pallas")}
+bases = {c: O.gen_bases(c, NMAX) for c in CURVES}
 pool = {c: O.gen_scalars(c, 0xF022, NMAX) for c in bases}
 t0, cases, bad = time.time(), 0, 0
 while time.time() - t0 < budget:
