@@ -734,6 +734,47 @@ int pc_hip_group_ligero_commit(pc_group* g, pc_curve field_of, const void* mat_h
 int pc_hip_group_ntt_batch(pc_group* g, pc_curve field_of, const void* in_host, size_t rows, size_t in_cols,
                            unsigned log_n, void* out_host);
 
+/* ---- ed_on_bls12_381 (JubJub): InnerProductArgPC over a twisted Edwards curve ----
+ * The curve the reference instantiates InnerProductArgPC on (ipa_pc/mod.rs:1056-1064: PC<EdwardsAffine, Blake2s256, UniPoly>;
+ * benches/ipa_times.rs:5,16): -x^2 + y^2 = 1 + d x^2 y^2 over BLS12-381's Fr, d = -10240/10241, cofactor 8, scalars modulo the 252-bit
+ * prime r.  It has an id space of its own (pc_te_curve), a typed key of its own (pc_te_srs: no pc_srs or pc_g2_srs entry point can be handed
+ * one, and none of these takes theirs) and entry points of its own, because a twisted Edwards point differs in kind: the law is complete,
+ * there is NO point at infinity and no infinity flag, and the identity is the ordinary point (0, 1).
+ * A point is x || y, two Montgomery residues of Fq, 64 bytes -- arkworks' twisted_edwards::Affine { x, y }; scalars are 32 bytes.
+ * Keys are not validated (as for pc_hip_srs_upload); an all-zero entry, which is not a curve point, counts as the identity.  Points
+ * outside the prime-order subgroup (orders 2, 4, 8 and their sums with subgroup points) are legal input everywhere: every product is
+ * exact integer arithmetic on the point it is given, as ark-ec's msm_bigint and mul_bigint are.
+ * On the device a key holds x || y || 2dxy per point (96 bytes, the third coordinate made once at upload: the bucket addition is 7
+ * multiplications with it and 9 without); upload, read-back and every result are x || y.  A pc_te_srs belongs to its context: counted by
+ * pc_hip_ctx_bytes_resident (out[0] and out[5]) and released by pc_hip_shutdown if the caller has not freed it (the handle then only
+ * remains to be freed).  The MSM is table-free: no window table, no GLV (the curve has no endomorphism), no captured launch graphs, no
+ * host-parts split, no many-MSM form.  The scalar field has 2-adicity 1: there are no Fr kernels (NTT, folds, pc_hip_ipa_open_rounds)
+ * for it; an opening folds its Fr vectors on the host. */
+typedef enum { PC_TE_ED_ON_BLS12_381 = 0 } pc_te_curve;
+typedef struct pc_te_srs pc_te_srs;
+/* The residency hook of InnerProductArgPC::trim (ipa_pc/mod.rs:359-401: comm_key copied at :384): n points x || y, stride_bytes
+ * between them (0: packed, 64; a device array must be packed).  Any pc_te_curve but PC_TE_ED_ON_BLS12_381: PC_ERR_INVALID_ARG. */
+int pc_hip_te_srs_upload(pc_ctx* ctx, pc_te_curve curve, const void* bases, size_t n, size_t stride_bytes, pc_mem where,
+                         pc_te_srs** out);
+void pc_hip_te_srs_free(pc_te_srs* srs);
+size_t pc_hip_te_srs_len(const pc_te_srs* srs);
+/* Points [offset, offset + count) of the key as x || y on the host: final_comm_key of an opening (ipa_pc/mod.rs:718). */
+int pc_hip_te_srs_read(pc_ctx* ctx, const pc_te_srs* srs, size_t offset, size_t count, void* out_host);
+/* {bases (96 bytes a point), 0, 0, pipeline workspace} -- the layout of pc_hip_srs_bytes_resident; there are no tables. */
+int pc_hip_te_srs_bytes_resident(const pc_te_srs* srs, size_t out[4]);
+/* <G::Group as VariableBaseMSM>::msm_bigint(&comm_key[base_offset..], scalars).into_affine(): cm_commit, ipa_pc/mod.rs:54-72, and with
+ * it the L and R of every round (:671-675), blocking.  min(n, len - base_offset) pairs, as msm_bigint truncates.  out_xy: x || y; the
+ * identity is written as (0, ONE) -- arkworks' Affine::zero() in Montgomery form -- with *out_is_identity = 1 (optional). */
+int pc_hip_te_msm(pc_ctx* ctx, const pc_te_srs* srs, size_t base_offset, const void* scalars, pc_scalar_form form, pc_mem where,
+                  size_t n, void* out_xy, int* out_is_identity);
+/* key[i] = affine(key[i] + u * key[n_half + i]), i < n_half, in place, as pc_hip_ec_fold: `k_l += k_r * u` and normalize_batch,
+ * ipa_pc/mod.rs:699-707.  u_host: one Fr, Montgomery.  The key keeps its length; the round's MSMs read its first n_half points. */
+int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* srs, size_t n_half, const void* u_host);
+/* Host utilities, no device needed (like pc_hip_points_sum / pc_hip_point_mul; ipa_pc/mod.rs:672,675 combine a few points on the
+ * host): the sum of `count` points; scalar (Montgomery Fr) times one point, the scalar taken as the integer it is. */
+int pc_hip_te_points_sum(pc_te_curve curve, const void* points, size_t count, void* out_xy);
+int pc_hip_te_point_mul(pc_te_curve curve, const void* point, const void* scalar_mont, void* out_xy);
+
 #ifdef __cplusplus
 }
 #endif

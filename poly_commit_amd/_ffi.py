@@ -8,6 +8,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 CURVES = {"bls12_381": 0, "bn254": 1, "pallas": 2, "bls12_377": 3}
 FQ_BYTES = {"bls12_381": 48, "bn254": 32, "pallas": 32, "bls12_377": 48}
+# the twisted Edwards curves (pc_te_curve): an id space of their own, with typed keys and entry points of their own
+TE_CURVES = {"ed_on_bls12_381": 0}
+TE_POINT_BYTES = {"ed_on_bls12_381": 64}
 PC_MEM_HOST, PC_MEM_DEVICE = 0, 1
 PC_SCALARS_CANONICAL, PC_SCALARS_MONTGOMERY = 0, 1
 
@@ -150,6 +153,17 @@ def load_library():
     lib.pc_hip_g2_msm.argtypes = [vp, vp, sz, vp, ip, ip, sz, vp, C.POINTER(ip)]
     lib.pc_hip_g2_points_sum.argtypes = [ip, vp, sz, vp]
     lib.pc_hip_g2_point_mul.argtypes = [ip, vp, vp, vp]
+    lib.pc_hip_te_srs_upload.argtypes = [vp, ip, vp, sz, sz, ip, C.POINTER(vp)]
+    lib.pc_hip_te_srs_free.argtypes = [vp]
+    lib.pc_hip_te_srs_free.restype = None
+    lib.pc_hip_te_srs_len.argtypes = [vp]
+    lib.pc_hip_te_srs_len.restype = sz
+    lib.pc_hip_te_srs_read.argtypes = [vp, vp, sz, sz, vp]
+    lib.pc_hip_te_srs_bytes_resident.argtypes = [vp, C.POINTER(sz)]
+    lib.pc_hip_te_msm.argtypes = [vp, vp, sz, vp, ip, ip, sz, vp, C.POINTER(ip)]
+    lib.pc_hip_te_ec_fold.argtypes = [vp, vp, sz, vp]
+    lib.pc_hip_te_points_sum.argtypes = [ip, vp, sz, vp]
+    lib.pc_hip_te_point_mul.argtypes = [ip, vp, vp, vp]
     lib.pc_hip_ml_fold.argtypes = [vp, ip, vp, sz, vp, vp, vp]
     lib.pc_hip_ml_open.argtypes = [vp, vp, vp, ip, C.c_uint, vp, vp, C.POINTER(ip)]
     lib.pc_hip_ml_eq_evals.argtypes = [vp, ip, vp, C.c_uint, vp]
@@ -559,6 +573,10 @@ class Context:
 
     def upload_g2_srs(self, curve, bases, n=None, stride_bytes=0):
         return G2Srs(self, curve, bases, n, stride_bytes)
+
+    def upload_te_srs(self, curve, bases, n=None, stride_bytes=0):
+        """A resident key of twisted Edwards points (pc_hip_te_srs_upload); curve: a name of TE_CURVES, bases: n x 64 bytes x || y."""
+        return TeSrs(self, curve, bases, n, stride_bytes)
 
     def ml_fold(self, curve, r_in_dev, n_half, z, r_out_dev, q_dev):
         """One halving round of MultilinearPC::open on device vectors (pc_hip_ml_fold); z: one Montgomery Fr (host)."""
@@ -1045,6 +1063,78 @@ class G2Srs:
         inf = (C.c_int * nv)()
         self.ctx.check(self.ctx.lib.pc_hip_ml_open(self.ctx.h, self.h, p, where, nv, C.c_void_p(point.ctypes.data), C.c_void_p(out.ctypes.data), inf))
         return out, [bool(x) for x in inf]
+
+
+class TeSrs:
+    """Resident twisted Edwards bases (pc_te_srs): the committer key of InnerProductArgPC over ed_on_bls12_381.  Points are 64 bytes,
+    x || y in Montgomery form, on the way in and out; the identity is (0, ONE), there is no infinity."""
+
+    def __init__(self, ctx, curve, bases, n=None, stride_bytes=0):
+        self.ctx, self.curve = ctx, curve
+        p, where = _ptr(bases)
+        if n is None:
+            n = bases.shape[0]
+        h = C.c_void_p()
+        ctx.check(ctx.lib.pc_hip_te_srs_upload(ctx.h, TE_CURVES[curve], p, n, stride_bytes, where, C.byref(h)))
+        self.h, self.n = h, n
+
+    def free(self):
+        if self.h:
+            self.ctx.lib.pc_hip_te_srs_free(self.h)
+            self.h = None
+
+    def __len__(self):
+        return int(self.ctx.lib.pc_hip_te_srs_len(self.h))
+
+    def bytes_resident(self):
+        out = (C.c_size_t * 4)()
+        self.ctx.check(self.ctx.lib.pc_hip_te_srs_bytes_resident(self.h, out))
+        return dict(zip(("bases", "window_tables", "fold_table", "lanes"), [int(x) for x in out]))
+
+    def read(self, offset, count):
+        out = np.zeros((count, TE_POINT_BYTES[self.curve]), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.pc_hip_te_srs_read(self.ctx.h, self.h, offset, count, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def msm(self, scalars, n=None, base_offset=0, montgomery=False):
+        """sum scalars[i] * bases[base_offset + i]; returns (64-byte uint8 array x || y, is_identity)."""
+        p, where = _ptr(scalars)
+        if n is None:
+            n = scalars.shape[0]
+        out = np.zeros(TE_POINT_BYTES[self.curve], dtype=np.uint8)
+        ident = C.c_int(0)
+        self.ctx.check(self.ctx.lib.pc_hip_te_msm(self.ctx.h, self.h, base_offset, p,
+                                                  PC_SCALARS_MONTGOMERY if montgomery else PC_SCALARS_CANONICAL,
+                                                  where, n, C.c_void_p(out.ctypes.data), C.byref(ident)))
+        return out, bool(ident.value)
+
+    def ec_fold(self, n_half, u_mont):
+        """key[i] = key[i] + u * key[n_half + i], i < n_half, in place (pc_hip_te_ec_fold); u_mont: one Montgomery Fr (host, 32 bytes)."""
+        u_mont = np.ascontiguousarray(u_mont)
+        self.ctx.check(self.ctx.lib.pc_hip_te_ec_fold(self.ctx.h, self.h, n_half, C.c_void_p(u_mont.ctypes.data)))
+
+
+def te_points_sum(curve, points):
+    """Host-side sum of twisted Edwards points (k x 64 bytes) -> one point."""
+    lib = load_library()
+    points = np.ascontiguousarray(points)
+    out = np.zeros(TE_POINT_BYTES[curve], dtype=np.uint8)
+    rc = lib.pc_hip_te_points_sum(TE_CURVES[curve], C.c_void_p(points.ctypes.data), points.shape[0], C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise PcHipError(rc, lib.pc_hip_strerror(rc).decode())
+    return out
+
+
+def te_point_mul(curve, point, scalar_mont):
+    """Host-side k * P for one twisted Edwards point and one Montgomery-form Fr (the scalar as the integer it is)."""
+    lib = load_library()
+    point = np.ascontiguousarray(point)
+    scalar_mont = np.ascontiguousarray(scalar_mont)
+    out = np.zeros(TE_POINT_BYTES[curve], dtype=np.uint8)
+    rc = lib.pc_hip_te_point_mul(TE_CURVES[curve], C.c_void_p(point.ctypes.data), C.c_void_p(scalar_mont.ctypes.data), C.c_void_p(out.ctypes.data))
+    if rc != 0:
+        raise PcHipError(rc, lib.pc_hip_strerror(rc).decode())
+    return out
 
 
 def ml_level_offset(nv, i):

@@ -27,7 +27,7 @@ int pc_hip_init(int device_id, pc_ctx** out) {
 void pc_hip_shutdown(pc_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  { std::lock_guard<std::recursive_mutex> lk(ctx->mu); keys_shutdown(ctx); g2_keys_shutdown(ctx); lincodes_shutdown(ctx); }
+  { std::lock_guard<std::recursive_mutex> lk(ctx->mu); keys_shutdown(ctx); g2_keys_shutdown(ctx); te_keys_shutdown(ctx); lincodes_shutdown(ctx); }
   ctx->ntt_plans.clear();
   if (ctx->epoch) (void)hipEventDestroy(ctx->epoch);
   for (hipStream_t q : ctx->lig_out_q) if (q) (void)hipStreamDestroy(q);
@@ -85,7 +85,7 @@ int pc_hip_ctx_bytes_resident(pc_ctx* ctx, size_t out[6]) {
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   for (int i = 0; i < 6; i++) out[i] = 0;
   out[0] = pc::dev_bytes_held(ctx->device);
-  out[5] = keys_bytes(ctx, out + 1) + ctx->g2_keys.size();      // (G2 keys: counted here and, through the ledger, in out[0])
+  out[5] = keys_bytes(ctx, out + 1) + ctx->g2_keys.size() + ctx->te_keys.size();      // (G2 and twisted Edwards keys: counted here and, through the ledger, in out[0])
   out[4] = ctx->be.scratch_bytes();
   return PC_OK;
 }
@@ -100,6 +100,7 @@ int pc_hip_ctx_trim(pc_ctx* ctx) {
     for (int i = 0; i < 3; i++) { ctx->be.free(ctx->ipa_buf[i]); ctx->ipa_buf[i] = nullptr; ctx->ipa_bytes[i] = 0; }      // pc_hip_ipa_open_rounds' vectors
     keys_trim(ctx);
     g2_keys_trim(ctx);
+    te_keys_trim(ctx);
     return (int)PC_OK;
   });
 }

@@ -1,0 +1,182 @@
+// C ABI of the gfx950 backend (include/pc_hip.h): the twisted Edwards curve ed_on_bls12_381 (JubJub) -- typed keys, the MSM and the key
+// fold of InnerProductArgPC over it (ipa_pc/mod.rs:54-72, 699-707).  This unit also instantiates everything templated on TeOf<T>
+// (te.hpp, MsmPlan<TeOf<T>, HipBackend> with the digit and sort stages of its scalar field), and nothing of a short Weierstrass group.
+#include <vector>
+#include "abi.hpp"
+#include "hip_backend_msm.hpp"
+#include "te.hpp"
+
+namespace pc {
+namespace {
+
+typedef TeOf<pc_te_ed_on_bls12_381> TeC;
+typedef TeC::FrP TeFrP;
+constexpr int TE_AW = AffD<TeC>::WORDS, TE_XY = AffD<TeC>::XY_WORDS, TE_XW = XyzzD<TeC>::WORDS, TE_FR_W = TeFrP::N, TE_FQ_W = TeC::FqP::N;
+constexpr size_t TE_POINT_BYTES = (size_t)TE_XY * 4;      // the caller's x || y
+constexpr uint32_t TE_NORM_K = 16;                        // points per inversion of the fold's normalisation (JacBatchAffineBody's default)
+
+// One blocking, table-free MSM pipeline: plain launches (no captured graphs), host scalars staged whole (no parts)
+struct TeRunnerT : TeRunner {
+  HipBackend& be;
+  MsmPlan<TeC, HipBackend> plan;
+  TeRunnerT(HipBackend& b, size_t n_max, const MsmConfig& cfg) : be(b), plan(b, n_max, cfg) {}
+  void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) override {
+    const uint32_t* sdev = (const uint32_t*)scalars;
+    be.n_ev = 0; be.mark();
+    if (where == PC_MEM_HOST) { be.copy_h2d(plan.scalar_staging(), scalars, n * (size_t)TE_FR_W * 4); sdev = plan.scalar_staging(); }
+    plan.run(bases, base_off, sdev, n, from_mont, out_host);
+  }
+};
+
+TeLane* te_lane(pc_te_srs* k) {
+  if (k->lane) return k->lane;
+  TeLane* L = new TeLane();
+  try {
+    L->be.init();
+    MsmConfig cfg = k->ctx->msm_cfg;
+    cfg.tbl = nullptr; cfg.tbl_c = 0;
+    cfg.coop2_max_points = 0;      // one lane per point in every cooperative level (the two-lane form is an XYZZ schedule)
+    L->runner = new TeRunnerT(L->be, k->n, cfg);
+  } catch (...) { delete L; throw; }
+  k->lane = L;
+  return L;
+}
+
+void write_identity(uint32_t* out_xy) {
+  for (int i = 0; i < TE_FQ_W; i++) { out_xy[i] = 0; out_xy[TE_FQ_W + i] = TeC::FqP::ONE[i]; }
+}
+
+}  // namespace
+}  // namespace pc
+
+using pc::TeC;
+using pc::TE_AW;
+using pc::TE_XY;
+using pc::TE_POINT_BYTES;
+
+static int te_curve_check(pc_te_curve curve) { return curve == PC_TE_ED_ON_BLS12_381 ? PC_OK : PC_ERR_INVALID_ARG; }
+
+extern "C" {
+
+int pc_hip_te_srs_upload(pc_ctx* ctx, pc_te_curve curve, const void* bases, size_t n, size_t stride_bytes, pc_mem where, pc_te_srs** out) {
+  if (!ctx || !out || (!bases && n)) return PC_ERR_INVALID_ARG;
+  if (int rc = te_curve_check(curve)) return rc;
+  if (where != PC_MEM_HOST && where != PC_MEM_DEVICE) return PC_ERR_INVALID_ARG;
+  if (stride_bytes == 0) stride_bytes = TE_POINT_BYTES;
+  if (stride_bytes < TE_POINT_BYTES) return PC_ERR_INVALID_ARG;
+  if (n >= (1ull << 31)) return PC_ERR_TOO_LARGE;
+  if (where == PC_MEM_DEVICE && stride_bytes != TE_POINT_BYTES) return PC_ERR_UNSUPPORTED;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  *out = nullptr;
+  pc_te_srs* k = nullptr;
+  int rc = guarded(ctx, [&]() {
+    k = te_key_create(ctx, curve, n, (size_t)TE_AW * 4);
+    if (!k) return (int)PC_ERR_OOM;
+    if (!n) return (int)PC_OK;
+    // the caller's points, packed (twisted_edwards::Affine has no flag behind its coordinates: a larger stride is only skipped)
+    std::vector<uint8_t> packed;
+    const void* src = bases;
+    if (where == PC_MEM_HOST && stride_bytes != TE_POINT_BYTES) {
+      packed.resize(n * TE_POINT_BYTES);
+      for (size_t i = 0; i < n; i++) memcpy(&packed[i * TE_POINT_BYTES], (const uint8_t*)bases + i * stride_bytes, TE_POINT_BYTES);
+      src = packed.data();
+    }
+    Staged xy(ctx->be, src, where, n * TE_POINT_BYTES, true, 0);
+    pc::TeDeriveBody<TeC> b{(const uint32_t*)xy.dev, k->bases};      // x || y -> x || y || 2 d x y
+    ctx->be.launch(b, n);
+    ctx->be.sync();
+    return (int)PC_OK;
+  });
+  if (rc != PC_OK) { if (k) te_key_free(k); return rc; }
+  *out = k;
+  return PC_OK;
+}
+
+void pc_hip_te_srs_free(pc_te_srs* k) { key_free_locked(k, te_key_free); }
+
+size_t pc_hip_te_srs_len(const pc_te_srs* k) { return k ? k->n : 0; }
+
+int pc_hip_te_srs_bytes_resident(const pc_te_srs* k, size_t out[4]) {
+  if (!k || !out) return PC_ERR_INVALID_ARG;
+  if (!k->ctx) { out[0] = out[1] = out[2] = out[3] = 0; return PC_OK; }
+  std::lock_guard<std::recursive_mutex> lk(k->ctx->mu);
+  te_key_bytes(k, out);
+  return PC_OK;
+}
+
+int pc_hip_te_srs_read(pc_ctx* ctx, const pc_te_srs* k, size_t offset, size_t count, void* out_host) {
+  if (!ctx || !k || k->ctx != ctx || offset > k->n || count > k->n - offset || (count && !out_host)) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    if (!count) return (int)PC_OK;
+    CallBuf xy(ctx->be, 1, count * TE_POINT_BYTES);
+    pc::TeStripBody<TeC> b{k->bases + offset * (size_t)TE_AW, (uint32_t*)xy.dev};
+    ctx->be.launch(b, count);
+    ctx->be.copy_d2h(out_host, xy.dev, count * TE_POINT_BYTES);
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_te_msm(pc_ctx* ctx, const pc_te_srs* kc, size_t base_offset, const void* scalars, pc_scalar_form form, pc_mem where, size_t n,
+                  void* out_xy, int* out_is_identity) {
+  pc_te_srs* k = const_cast<pc_te_srs*>(kc);
+  if (!ctx || !k || !out_xy || k->ctx != ctx || base_offset > k->n) return PC_ERR_INVALID_ARG;
+  if (where != PC_MEM_HOST && where != PC_MEM_DEVICE) return PC_ERR_INVALID_ARG;
+  if (form != PC_SCALARS_CANONICAL && form != PC_SCALARS_MONTGOMERY) return PC_ERR_INVALID_ARG;
+  const size_t avail = k->n - base_offset;      // msm_bigint semantics: min(bases.len(), scalars.len()) pairs
+  if (n > avail) n = avail;
+  if (n && !scalars) return PC_ERR_INVALID_ARG;
+  if (!n) {                                      // the empty sum: the identity, no device work
+    pc::write_identity((uint32_t*)out_xy);
+    if (out_is_identity) *out_is_identity = 1;
+    return PC_OK;
+  }
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    TeLane* L = pc::te_lane(k);
+    L->be.timing = ctx->be.timing;
+    L->runner->run(k->bases, (uint32_t)base_offset, scalars, where, n, form == PC_SCALARS_MONTGOMERY, (uint32_t*)out_xy);
+    if (out_is_identity) *out_is_identity = pc::host64::te_is_identity<pc_te_ed_on_bls12_381>((const uint32_t*)out_xy) ? 1 : 0;
+    // phase brackets of the call (pc_hip_last_msm_phases_ms), as for a G1 pipeline
+    for (int i = 0; i < 8; i++) ctx->phases[i] = 0;
+    if (L->be.timing) for (int i = 0; i + 1 < L->be.n_ev && i < 8; i++) (void)hipEventElapsedTime(&ctx->phases[i], L->be.ev[i], L->be.ev[i + 1]);
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* k, size_t n_half, const void* u_host) {
+  if (!ctx || !k || k->ctx != ctx || !u_host || 2 * n_half > k->n) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    if (!n_half) return (int)PC_OK;
+    pc::HipBackend& be = ctx->be;
+    // the sums in extended coordinates, then the prefix products of the normalisation
+    uint32_t* ext = (uint32_t*)be.workspace(n_half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);
+    uint32_t* scratch = ext + n_half * (size_t)pc::TE_XW;
+    pc::TeEcFoldBody<TeC> f;
+    f.key = k->bases; f.half = (uint32_t)n_half; f.ext = ext;
+    const pc::Fd<pc::TeFrP> u = pc::Fd<pc::TeFrP>::load((const uint32_t*)u_host).from_mont();
+    f.naf.from_scalar(u.l);
+    be.launch(f, n_half);
+    pc::TeBatchAffineBody<TeC> nb{ext, scratch, k->bases, (uint32_t)n_half, pc::TE_NORM_K};
+    be.launch(nb, (n_half + pc::TE_NORM_K - 1) / pc::TE_NORM_K);
+    be.sync();
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_te_points_sum(pc_te_curve curve, const void* points, size_t count, void* out_xy) {
+  if (!out_xy || (count && !points)) return PC_ERR_INVALID_ARG;
+  if (int rc = te_curve_check(curve)) return rc;
+  pc::host64::points_sum<TeC>((const uint32_t*)points, count, (uint32_t*)out_xy);
+  return PC_OK;
+}
+
+int pc_hip_te_point_mul(pc_te_curve curve, const void* point, const void* scalar_mont, void* out_xy) {
+  if (!point || !scalar_mont || !out_xy) return PC_ERR_INVALID_ARG;
+  if (int rc = te_curve_check(curve)) return rc;
+  pc::host64::scalar_mul<TeC>((const uint32_t*)point, pc::Fd<pc::TeFrP>::load((const uint32_t*)scalar_mont).from_mont().l, (uint32_t*)out_xy);
+  return PC_OK;
+}
+
+}  // extern "C"

@@ -26,6 +26,23 @@ template <class C1> struct CoordOf<G2Of<C1>> { typedef Fq2D<typename C1::FqP> ty
 // the curve whose scalars a group's MSM sorts (the sort stage only looks at scalars)
 template <class C> struct ScalarCurveOf { typedef C type; static constexpr bool IS_G2 = false; };
 template <class C1> struct ScalarCurveOf<G2Of<C1>> { typedef C1 type; static constexpr bool IS_G2 = true; };
+// TeOf<T>: the group of a twisted Edwards curve T (te_constants.h) with a = -1, coordinates over T::FqP, scalars over T::FrP.  Its
+// point types are the specialisations of te.hpp: an extended (X, Y, Z, T) bucket under a complete law, no infinity -- the all-zero
+// words only mean "empty".  The sort stage is instantiated for the tag itself (it only looks at FrP).
+// (measurement switch, never set in the product build: PC_TE_DERIVED_TD=0 keeps a base as the bare x || y, 2 N words, and makes 2 d x y
+// inside every mixed addition -- 9M instead of 7M against a 64-byte instead of a 96-byte gather; profiles/EXPERIMENTS.md)
+#ifndef PC_TE_DERIVED_TD
+#define PC_TE_DERIVED_TD 1
+#endif
+template <class T> struct TeOf { typedef T Curve; typedef typename T::FqP FqP; typedef typename T::FrP FrP; };
+template <class T> struct CoordOf<TeOf<T>> { typedef Fd<typename T::FqP> type; };
+template <class T> struct ScalarCurveOf<TeOf<T>> { typedef TeOf<T> type; static constexpr bool IS_G2 = false; };
+// What the MSM templates ask of a group beyond its point types.  TABLE_FREE: no window table, no GLV split, no many-MSM mode
+// (MsmPlan refuses them).  TWO_LANE: HalfAdd below, the XYZZ addition spread over a lane pair, exists for it.
+template <class C> struct GroupKind {
+  static constexpr bool IS_TE = false, TABLE_FREE = ScalarCurveOf<C>::IS_G2, TWO_LANE = !ScalarCurveOf<C>::IS_G2;
+};
+template <class T> struct GroupKind<TeOf<T>> { static constexpr bool IS_TE = true, TABLE_FREE = true, TWO_LANE = false; };
 
 template <class C>
 struct AffD {

@@ -16,6 +16,10 @@ template <> struct GlvOf<pc_curve_bn254> { typedef pc_glv_bn254 T; };
 template <> struct GlvOf<pc_curve_pallas> { typedef pc_glv_pallas T; };
 template <> struct GlvOf<pc_curve_bls12_377> { typedef pc_glv_bls12_377 T; };
 
+// whether a curve has the endomorphism at all (a twisted Edwards group, te.hpp, does not: its digit stage never splits)
+template <class C, class = void> struct HasGlv { static constexpr bool value = false; };
+template <class C> struct HasGlv<C, decltype((void)sizeof(GlvOf<C>))> { static constexpr bool value = true; };
+
 struct GlvSplit { uint32_t k1[5], k2[5]; uint32_t neg1, neg2; };   // sign-magnitude, 160-bit magnitudes
 
 namespace glv_host {

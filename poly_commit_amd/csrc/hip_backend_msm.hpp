@@ -31,7 +31,7 @@ void HipBackend::sort_entries(const MsmGeom& g, const uint32_t* scalars, uint32_
   uint2* records = (uint2*)((char*)sort_ws + rec_off);
   const size_t lds = (size_t)sg.NC * 4;
   uint32_t* split = (uint32_t*)((char*)sort_ws + split_off);
-  if (g.glv) {      // k = k1 + k2 lambda once per scalar (Montgomery -> canonical fused): both passes below read the 40-byte records
+  if constexpr (HasGlv<C>::value) if (g.glv) {      // k = k1 + k2 lambda once per scalar (Montgomery -> canonical fused): both passes below read the 40-byte records
     GlvPresplitBody<C> b{g, scalars, split};
     launch(b, g.n);
   }
@@ -93,7 +93,8 @@ void HipBackend::bucket_level(uint32_t K, uint32_t weight_off, uint32_t cnt, uin
     // and keeps K <= 128: its tile of K points then fits the 64 KiB a launch may ask for without an attribute)
     if constexpr (ScalarCurveOf<C>::IS_G2) { if (mode == 2 || K > 128) throw std::runtime_error("bucket_level: G2 levels are one lane per point, K <= 128"); }
     bool two_lane = false;
-    if constexpr (!ScalarCurveOf<C>::IS_G2) {
+    if constexpr (!GroupKind<C>::TWO_LANE && !ScalarCurveOf<C>::IS_G2) { if (mode == 2) throw std::runtime_error("bucket_level: this group has no two-lane levels"); }
+    if constexpr (GroupKind<C>::TWO_LANE) {
       if (mode == 2 && K <= 128) {
         two_lane = true;
         hipLaunchKernelGGL(k_bucket_level_coop2<C>, dim3(cnt * (1 + n_old)), dim3(2 * K), lds, stream, K, lgK, weight_off, cnt, n_old, x,

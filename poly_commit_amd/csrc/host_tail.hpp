@@ -108,10 +108,13 @@ struct F64x2 {
 
 }  // namespace host64
 template <class C1> struct G2Of;      // ec.hpp
+template <class T> struct TeOf;       // ec.hpp; its host point, Xyzz64<TeOf<T>>, is in te.hpp
 template <class C> struct AffD;
 template <class C> struct XyzzD;
 namespace host64 {
 template <class C> struct Coord64Of { typedef F64<typename C::FqP> type; };
+template <class C> struct IsTe { static constexpr bool value = false; };
+template <class T> struct IsTe<TeOf<T>> { static constexpr bool value = true; };
 template <class C1> struct Coord64Of<G2Of<C1>> { typedef F64x2<typename C1::FqP> type; };
 
 template <class C>
@@ -174,9 +177,12 @@ void scalar_mul(const uint32_t* pt, const uint32_t* k_canonical, uint32_t* out_a
 // out = the sum of `count` affine points of G as an affine point (the group law of the device code, ec.hpp, run on the host)
 template <class G>
 void points_sum(const uint32_t* pts, size_t count, uint32_t* out_affine) {
+  if constexpr (IsTe<G>::value) { Xyzz64<G>::points_sum(pts, count, out_affine); return; }      // (the caller's points are x || y, the device's affine form is not)
+  else {
   XyzzD<G> acc = XyzzD<G>::infinity();
   for (size_t i = 0; i < count; i++) acc.add_affine(AffD<G>::load(pts + i * AffD<G>::WORDS));
   acc.to_affine().store(out_affine);
+  }
 }
 
 struct WeightedPoint { uint32_t exponent; const uint32_t* xyzz; };
@@ -199,6 +205,8 @@ void horner_to_affine(std::vector<WeightedPoint>& items, uint32_t* out_affine) {
 // inversion (Montgomery's trick over the products ZZ*ZZZ).
 template <class C>
 void batch_to_affine(const uint32_t* xyzz, size_t count, uint32_t* out_affine) {
+  if constexpr (IsTe<C>::value) { Xyzz64<C>::batch_to_affine(xyzz, count, out_affine); return; }
+  else {
   typedef Xyzz64<C> P; typedef typename P::Fq Fq;
   constexpr int FW = P::FW;
   std::vector<Fq> prefix(count);
@@ -216,6 +224,7 @@ void batch_to_affine(const uint32_t* xyzz, size_t count, uint32_t* out_affine) {
     Fq t = inv.mul(prefix[i]);                 // 1 / (ZZ * ZZZ) of point i
     inv = inv.mul(p.ZZ.mul(p.ZZZ));
     p.X.mul(t.mul(p.ZZZ)).store(o); p.Y.mul(t.mul(p.ZZ)).store(o + FW);
+  }
   }
 }
 

@@ -46,6 +46,7 @@ struct pc_ctx {
   // pc_hip_ipa_open_rounds: the powers of z, the per-base factors of the fixed key and the two scalar vectors of its rounds (grow-only, pc_hip_ctx_trim frees them)
   void* ipa_buf[3] = {nullptr, nullptr, nullptr}; size_t ipa_bytes[3] = {0, 0, 0};
   std::vector<struct pc_g2_srs*> g2_keys;   // every G2 key object of this context that is alive (the functions at the end of this header own them)
+  std::vector<struct pc_te_srs*> te_keys;   // every twisted Edwards key object of this context that is alive (the functions at the end of this header own them)
   std::vector<struct pc_lincode*> codes;   // every Brakedown code object of this context that is alive; abi_lincode.hip alone creates and releases them
   float brakedown_phases[4] = {0, 0, 0, 0};
   uint32_t skzg_launches[2] = {0, 0};      // kernel launches of the last streaming_kzg call: [folding tree, divisions + combination] (pc_hip_last_skzg_launches)
@@ -57,7 +58,7 @@ struct pc_key_base {
   pc_ctx* ctx = nullptr;         // null: the context was shut down under the key (a tombstone: nothing left to release)
   pc_curve curve = PC_CURVE_BLS12_381;
   size_t n = 0;
-  uint32_t* bases = nullptr;     // packed coordinates: x||y (G1), x.c0 || x.c1 || y.c0 || y.c1 (G2); all zero = infinity
+  uint32_t* bases = nullptr;     // packed coordinates: x||y (G1), x.c0 || x.c1 || y.c0 || y.c1 (G2); all zero = infinity.  A twisted Edwards key: x || y || 2dxy
   int aw = 0;                    // words per affine point
 };
 
@@ -517,4 +518,41 @@ inline void g2_keys_shutdown(pc_ctx* ctx) { key_registry_shutdown(ctx->g2_keys, 
 // pc_hip_ctx_trim's share: an idle pipeline gives its sort / scan scratch back
 inline void g2_keys_trim(pc_ctx* ctx) {
   for (pc_g2_srs* k : ctx->g2_keys) if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }
+}
+
+// ---- twisted Edwards keys --------------------------------------------------------------------
+// A key of ed_on_bls12_381 points (pc_hip_te_srs_upload): a type of its own, as pc_g2_srs is, so that no short Weierstrass entry point can
+// be handed one -- its points have another law and no infinity.  Resident form: x || y || td with td = 2 d x y made at upload (te.hpp),
+// 3 Fq = 96 bytes a point, where the caller's is 64; `aw` counts the resident words, `curve` is unused.  Same rules as pc_g2_srs:
+// registered in its context, released with it (a tombstone stays behind), one pipeline, created on first use by abi_te.hip.
+struct TeLane {
+  pc::HipBackend be;
+  pc::TeRunner* runner = nullptr;
+  ~TeLane() { delete runner; be.destroy(); }
+};
+struct pc_te_srs : pc_key_base {
+  pc_te_curve te_curve = PC_TE_ED_ON_BLS12_381;
+  TeLane* lane = nullptr;
+};
+inline void te_key_release_device(pc_te_srs* k) {
+  if (!k->ctx) return;
+  (void)hipSetDevice(k->ctx->device);
+  delete k->lane; k->lane = nullptr;
+  key_base_release(k->ctx->te_keys, k);
+}
+inline void te_key_free(pc_te_srs* k) { te_key_release_device(k); delete k; }
+// call inside guarded(): a failed device allocation throws, with the object already released.  Null: no host memory.
+inline pc_te_srs* te_key_create(pc_ctx* ctx, pc_te_curve curve, size_t n, size_t resident_point_bytes) {
+  pc_te_srs* k = key_base_create(ctx->te_keys, ctx, PC_CURVE_BLS12_381, n, resident_point_bytes, te_key_free);
+  if (k) k->te_curve = curve;
+  return k;
+}
+// {bases, 0, 0, pipeline} bytes of one key (the layout of key_bytes: no tables)
+inline void te_key_bytes(const pc_te_srs* k, size_t out[4]) {
+  out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = out[2] = 0;
+  out[3] = k->lane ? k->lane->be.bytes_live : 0;
+}
+inline void te_keys_shutdown(pc_ctx* ctx) { key_registry_shutdown(ctx->te_keys, te_key_release_device); }
+inline void te_keys_trim(pc_ctx* ctx) {
+  for (pc_te_srs* k : ctx->te_keys) if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }
 }

@@ -55,6 +55,12 @@
     asm volatile("" ::"v"(IDX));                                                                                        \
   } while (0)
 #define PC_ARRIVED_WORD(W) asm volatile("" ::"v"(W))
+// the derived coordinate of a twisted Edwards base (te.hpp: x, y, td)
+#define PC_ARRIVED_TD(PT)                                                                                               \
+  do {                                                                                                                  \
+    constexpr int PC_N_ = sizeof((PT).td.l) / 4;                                                                        \
+    for (int pc_i_ = 0; pc_i_ < PC_N_; pc_i_ += 4) asm volatile("" ::"v"((PT).td.l[pc_i_]));                          \
+  } while (0)
 // the same for a point over Fq2 (four coefficients per point)
 #define PC_ARRIVED_FQ2(PT, IDX)                                                                                         \
   do {                                                                                                                  \
@@ -66,6 +72,7 @@
 #else
 #define PC_ARRIVED(PT, IDX) ((void)0)
 #define PC_ARRIVED_FQ2(PT, IDX) ((void)0)
+#define PC_ARRIVED_TD(PT) ((void)0)
 #define PC_ARRIVED_WORD(W) ((void)0)
 #endif
 
@@ -241,7 +248,8 @@ struct GlvPresplitBody {
 // parameter -- the split's temporaries would triple the registers of the plain passes, 33 -> 94 VGPRs, and halve their occupancy)
 template <class C, class Geo, class F>
 PC_HD void for_each_signed_digit(const Geo& g, const uint32_t* scalar, F f) {
-  if (g.glv) for_each_signed_digit_t<C, 1>(g, scalar, f); else for_each_signed_digit_t<C, 0>(g, scalar, f);
+  if constexpr (HasGlv<C>::value) { if (g.glv) { for_each_signed_digit_t<C, 1>(g, scalar, f); return; } }      // (no endomorphism: no split to instantiate)
+  for_each_signed_digit_t<C, 0>(g, scalar, f);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -389,6 +397,9 @@ struct AccumulateBody {
         // in order, so the compiler's own wait -- at the first use of `pt`, behind that block -- became vmcnt(0) over the just-issued
         // stores: every wave sat out a store round trip on the iterations in which one of its lanes crosses a bucket boundary.
         if constexpr (ScalarCurveOf<C>::IS_G2) PC_ARRIVED_FQ2(pt, nval); else PC_ARRIVED(pt, nval);
+#if PC_TE_DERIVED_TD
+        if constexpr (GroupKind<C>::IS_TE) PC_ARRIVED_TD(pt);      // the third coordinate of a twisted Edwards base (te.hpp)
+#endif
         PC_ARRIVED_WORD(next_boundary);
         // Bucket boundary.  NOTHING in this block may wait on memory: some lane of a wave crosses a boundary in 50 % (96 entries per
         // bucket) to 90 % (26) of the iterations.  Until round 4 the look-ahead offsets[k + 2] was loaded HERE -- the compiler
@@ -870,14 +881,14 @@ class MsmPlan {
   typedef XyzzD<C> Pt;
   typedef typename C::FrP FrP;
   typedef typename ScalarCurveOf<C>::type SC;      // the sort stage is instantiated for the curve of the scalars (G2: the pairing curve)
-  static constexpr bool G2 = ScalarCurveOf<C>::IS_G2;      // no window table, no GLV split for G2
+  static constexpr bool G2 = GroupKind<C>::TABLE_FREE;      // no window table, no GLV split for G2 and for a twisted Edwards group
   static constexpr int AW = AffD<C>::WORDS;
 
   // subs == 0: one MSM of up to n_max pairs per call.  subs == B > 0: every call is B independent MSMs of
   // n_max / B pairs over the same bases (cfg.tbl must hold their window table); see enqueue().
   MsmPlan(Backend& be, size_t n_max, const MsmConfig& cfg, uint32_t subs = 0) : be_(be), cfg_(cfg), n_max_(n_max), subs_(subs) {
     if (subs_ && (!cfg_.tbl || !cfg_.tbl_c || n_max % subs_)) throw std::runtime_error("MsmPlan: many-MSM mode needs a window table");
-    if (G2 && (subs_ || cfg_.tbl)) throw std::runtime_error("MsmPlan: G2 is table-free");
+    if (G2 && (subs_ || cfg_.tbl)) throw std::runtime_error("MsmPlan: G2 and twisted Edwards groups are table-free");
     if (cfg_.T2 < 4) cfg_.T2 = 4;       // each level must shrink the list: 2*ceil(s/T2) < s
     if (cfg_.T2b < 4) cfg_.T2b = 4;
     // plan_geometry divides the bucket count by these and turns them into Horner exponents: powers of two only

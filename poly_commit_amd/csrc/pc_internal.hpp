@@ -10,6 +10,7 @@
 //   abi.hpp            host only: the staging helpers more than one abi unit uses
 //   curve_<name>.hip   everything templated on one curve: MSM pipeline, window table, key fold, fixed-base mul, pair sums
 //   abi_g2.hip         beside its entry points, everything templated on G2 (BLS12-381 only); it instantiates no G1 kernel
+//   abi_te.hip         the same for the twisted Edwards group ed_on_bls12_381 (te.hpp): typed keys, MSM, key fold
 //   fixed_base.hpp     the group-generic launch sequences (fixed-base batch multiplication, pair sums): one copy, instantiated for
 //                      G1 by the curve units and for G2 by abi_g2.hip
 //   host_tail.hpp      host only: 64-bit-limb points of either group -- the MSM's Horner tail, affine -> XYZZ, one scalar
@@ -50,6 +51,13 @@ struct MsmRunner {
 struct G2Runner {
   virtual ~G2Runner() {}
   // out_host: the affine sum, 4 Fq (all zero = infinity)
+  virtual void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) = 0;
+};
+
+// One twisted Edwards MSM pipeline (abi_te.hip makes it: MsmPlan<TeOf<T>, HipBackend>, blocking, table-free)
+struct TeRunner {
+  virtual ~TeRunner() {}
+  // n >= 1 pairs; out_host: the affine sum x || y, 2 Fq (the identity is (0, 1))
   virtual void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) = 0;
 };
 

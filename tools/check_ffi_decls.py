@@ -16,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "pc_hip.h")
 FFI_RS = os.path.join(ROOT, "rust", "poly-commit-hip", "src", "ffi.rs")
 
-OPAQUE = ("pc_ctx", "pc_srs", "pc_job", "pc_lincode", "pc_g2_srs", "pc_group", "pc_group_srs", "pc_group_job")
-ENUMS = ("pc_curve", "pc_scalar_form", "pc_mem", "pc_hash", "pc_status")
+OPAQUE = ("pc_ctx", "pc_srs", "pc_job", "pc_lincode", "pc_g2_srs", "pc_te_srs", "pc_group", "pc_group_srs", "pc_group_job")
+ENUMS = ("pc_curve", "pc_te_curve", "pc_scalar_form", "pc_mem", "pc_hash", "pc_status")
 CALLBACKS = ("pc_ipa_challenge_fn",)          # function-pointer typedefs of the header, declared as `pub type` aliases in ffi.rs
 
 

@@ -37,6 +37,9 @@ GROUPS = [
     ("MarlinPST13 in the dense lexicographic layout: powers_of_beta of setup (marlin_pst13_pc/mod.rs:187-207), divide_at_point (:44-92), commit (:353-362), open (:419-512), trim's selection (:283-288); the layout helpers sort a BTreeMap key into device order",
      ["pc_hip_pst13_key_len", "pc_hip_pst13_rank", "pc_hip_pst13_unrank", "pc_hip_pst13_monomial_evals", "pc_hip_pst13_scatter", "pc_hip_pst13_divide", "pc_hip_pst13_commit",
       "pc_hip_pst13_open", "pc_hip_pst13_trim"]),
+    ("InnerProductArgPC over the twisted Edwards curve ed_on_bls12_381, the reference's own instantiation (ipa_pc/mod.rs:1056-1064): cm_commit's msm_bigint (:54-72), the key fold of open (:699-707), the key's residency (trim, :359-401)",
+     ["pc_hip_te_srs_upload", "pc_hip_te_srs_free", "pc_hip_te_srs_len", "pc_hip_te_srs_read", "pc_hip_te_srs_bytes_resident", "pc_hip_te_msm", "pc_hip_te_ec_fold",
+      "pc_hip_te_points_sum", "pc_hip_te_point_mul"]),
     ("one committer key over the GPUs of a node, one process",
      ["pc_hip_group_create", "pc_hip_group_destroy", "pc_hip_group_size", "pc_hip_group_ctx", "pc_hip_group_srs_upload", "pc_hip_group_srs_free",
       "pc_hip_group_srs_len", "pc_hip_group_msm", "pc_hip_group_msm_batch", "pc_hip_group_kzg_open", "pc_hip_group_commit_open_async", "pc_hip_group_job_wait", "pc_hip_group_ntt_batch", "pc_hip_group_ligero_commit"]),
@@ -52,7 +55,7 @@ HEAD = '''//! Raw declarations of the C ABI of `libpc_hip.so` (`include/pc_hip.h
 use core::ffi::{c_char, c_int, c_uint, c_void};
 
 macro_rules! opaque { ($($n:ident),*) => { $( #[repr(C)] pub struct $n { _p: [u8; 0], _m: core::marker::PhantomData<(*mut u8, core::marker::PhantomPinned)> } )* } }
-opaque!(pc_ctx, pc_srs, pc_job, pc_lincode, pc_g2_srs, pc_group, pc_group_srs, pc_group_job);
+opaque!(pc_ctx, pc_srs, pc_job, pc_lincode, pc_g2_srs, pc_te_srs, pc_group, pc_group_srs, pc_group_job);
 
 /// `pc_ipa_challenge_fn`: the caller's transcript inside `pc_hip_ipa_open_rounds` (user, l, r -> u; points as x || y, u as Montgomery limbs)
 pub type pc_ipa_challenge_fn = Option<unsafe extern "C" fn(user: *mut c_void, l_xy: *const c_void, r_xy: *const c_void, out_u_mont: *mut c_void)>;
@@ -71,6 +74,7 @@ def main():
     def const_block(title, keys):
         return f"// {title}\n" + "".join(f"pub const {k}: c_int = {enums[k] if k in enums else defs[k]};\n" for k in keys)
     out.append(const_block("pc_curve", ["PC_CURVE_BLS12_381", "PC_CURVE_BN254", "PC_CURVE_PALLAS", "PC_CURVE_BLS12_377"]))
+    out.append(const_block("pc_te_curve: the twisted Edwards curves (an id space of their own)", ["PC_TE_ED_ON_BLS12_381"]))
     out.append(const_block("pc_scalar_form: CANONICAL = &[F::BigInt] (msm_bigint's argument); MONTGOMERY = &[F] as poly.coeffs() lies in memory",
                            ["PC_SCALARS_CANONICAL", "PC_SCALARS_MONTGOMERY"]))
     out.append(const_block("pc_mem", ["PC_MEM_HOST", "PC_MEM_DEVICE"]))
