@@ -748,8 +748,9 @@ int pc_hip_group_ntt_batch(pc_group* g, pc_curve field_of, const void* in_host, 
  * multiplications with it and 9 without); upload, read-back and every result are x || y.  A pc_te_srs belongs to its context: counted by
  * pc_hip_ctx_bytes_resident (out[0] and out[5]) and released by pc_hip_shutdown if the caller has not freed it (the handle then only
  * remains to be freed).  The MSM is table-free: no window table, no GLV (the curve has no endomorphism), no captured launch graphs, no
- * host-parts split, no many-MSM form.  The scalar field has 2-adicity 1: there are no Fr kernels (NTT, folds, pc_hip_ipa_open_rounds)
- * for it; an opening folds its Fr vectors on the host. */
+ * host-parts split, no many-MSM form.  The scalar field has 2-adicity 1, so there is no NTT over it; the vector kernels of the halving
+ * rounds exist for it (pc_hip_te_fr_powers, pc_hip_te_ipa_fold_dots, pc_hip_te_ipa_key_scalars), and an opening runs on the device in
+ * one call, pc_hip_te_ipa_open_rounds, against a committer key that stays resident and unmodified. */
 typedef enum { PC_TE_ED_ON_BLS12_381 = 0 } pc_te_curve;
 typedef struct pc_te_srs pc_te_srs;
 /* The residency hook of InnerProductArgPC::trim (ipa_pc/mod.rs:359-401: comm_key copied at :384): n points x || y, stride_bytes
@@ -760,7 +761,7 @@ void pc_hip_te_srs_free(pc_te_srs* srs);
 size_t pc_hip_te_srs_len(const pc_te_srs* srs);
 /* Points [offset, offset + count) of the key as x || y on the host: final_comm_key of an opening (ipa_pc/mod.rs:718). */
 int pc_hip_te_srs_read(pc_ctx* ctx, const pc_te_srs* srs, size_t offset, size_t count, void* out_host);
-/* {bases (96 bytes a point), 0, 0, pipeline workspace} -- the layout of pc_hip_srs_bytes_resident; there are no tables. */
+/* {bases (96 bytes a point), 0, fold table, pipeline workspace} -- the layout of pc_hip_srs_bytes_resident; there are no window tables. */
 int pc_hip_te_srs_bytes_resident(const pc_te_srs* srs, size_t out[4]);
 /* <G::Group as VariableBaseMSM>::msm_bigint(&comm_key[base_offset..], scalars).into_affine(): cm_commit, ipa_pc/mod.rs:54-72, and with
  * it the L and R of every round (:671-675), blocking.  min(n, len - base_offset) pairs, as msm_bigint truncates.  out_xy: x || y; the
@@ -770,6 +771,42 @@ int pc_hip_te_msm(pc_ctx* ctx, const pc_te_srs* srs, size_t base_offset, const v
 /* key[i] = affine(key[i] + u * key[n_half + i]), i < n_half, in place, as pc_hip_ec_fold: `k_l += k_r * u` and normalize_batch,
  * ipa_pc/mod.rs:699-707.  u_host: one Fr, Montgomery.  The key keeps its length; the round's MSMs read its first n_half points. */
 int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* srs, size_t n_half, const void* u_host);
+/* out[i] = affine(src[i] + u * src[n_half + i]), i < n_half, as a NEW resident key of n_half points (the caller frees it); src is
+ * untouched -- the first fold of an opening against a committer key that stays resident.  If src has a fold table
+ * (pc_hip_te_srs_precompute_fold) and n_half is half its length, the points come from the table: one mixed addition per non-zero NAF
+ * digit of the canonical u.  In every other case (no table, another n_half, a digit beyond the table's rows) the ladder of
+ * pc_hip_te_ec_fold runs.  Either way the arithmetic is the same exact integer combination: the result is the same, bit for bit. */
+int pc_hip_te_ec_fold_from(pc_ctx* ctx, const pc_te_srs* src, size_t n_half, const void* u_host, pc_te_srs** out);
+/* Fold table of a committer key, once per key: T[b][j] = 2^b * key[n/2 + j] for b < 253 (the NAF positions of a 252-bit scalar, carry
+ * included), row-major in j, 96 bytes a record: 253 * n/2 * 96 bytes (12.7 GB for 2^20 points, 51 GB for 2^22).  n must be even.
+ * PC_ERR_UNSUPPORTED when the table would exceed the share of the free device memory that pc_hip_srs_precompute_fold allows
+ * (PC_HIP_FOLD_TABLE_MAX_FRAC).  Reported in out[2] of pc_hip_te_srs_bytes_resident and out[3] of pc_hip_ctx_bytes_resident; released
+ * by pc_hip_te_srs_free, pc_hip_shutdown and by pc_hip_te_ec_fold on this key (which changes the points it was made from). */
+int pc_hip_te_srs_precompute_fold(pc_ctx* ctx, pc_te_srs* srs);
+/* Rows of the key's fold table (0: no table). */
+int pc_hip_te_srs_fold_table_info(const pc_te_srs* srs, unsigned* out_rows);
+/* *out = 1 if every point of the key lies in the prime-order subgroup (r * P is the identity; an all-zero entry counts as the
+ * identity), else 0.  One ladder per point the first time, then the cached answer.  The fixed-key rounds of pc_hip_te_ipa_open_rounds
+ * multiply scalars modulo r before they meet a base, which is exact only on such a key; sample_generators makes such keys
+ * (mul_by_cofactor_to_group, ipa_pc/mod.rs:320), the ABI does not require them. */
+int pc_hip_te_srs_in_subgroup(pc_ctx* ctx, pc_te_srs* srs, int* out);
+/* The vector kernels of the halving rounds over the curve's scalar field: contracts, argument checks and error codes of
+ * pc_hip_fr_powers, pc_hip_ipa_fold_dots and pc_hip_ipa_key_scalars, with a pc_te_curve where those take the pc_curve of the field. */
+int pc_hip_te_fr_powers(pc_ctx* ctx, pc_te_curve curve, const void* z_host, size_t n, void* out_dev);
+int pc_hip_te_ipa_fold_dots(pc_ctx* ctx, pc_te_curve curve, void* coeffs_dev, void* z_dev, size_t m, const void* u_host, const void* u_inv_host,
+                            void* out_dots_host);
+int pc_hip_te_ipa_key_scalars(pc_ctx* ctx, pc_te_curve curve, const void* coeffs_dev, size_t m, void* s_dev, size_t n0,
+                              const void* fold_u_host, size_t fold_m, void* out_l_dev, void* out_r_dev);
+/* The halving rounds of InnerProductArgPC::open (ipa_pc/mod.rs:664-711) in one call, as pc_hip_ipa_open_rounds: arguments and outputs
+ * are that call's, with 64-byte points x || y (the identity is (0, ONE)).  Plain launches, no captured graphs; the two MSMs of a round
+ * run one after the other on the key's pipeline.  The committer key is never modified: the first fold is out of place (from the fold
+ * table when the key has one and n is its length), later folds are in place on the working key.  coeffs_dev is consumed.
+ * fixed_key_below: once the round size is <= it the key stays fixed and per-base factors carry the folds (0: the library's default,
+ * 2^16; 1: never).  That route is taken only on a committer key that passes pc_hip_te_srs_in_subgroup, asked here if it has not been;
+ * on any other key every round folds and the result stays integer-exact: not an error. */
+int pc_hip_te_ipa_open_rounds(pc_ctx* ctx, const pc_te_srs* comm_key, void* coeffs_dev, size_t n, const void* point_host, const void* h_prime_xy_host,
+                              pc_ipa_challenge_fn next_challenge, void* user, size_t fixed_key_below,
+                              void* out_l_vec_xy, void* out_r_vec_xy, void* out_final_key_xy, void* out_c_host, float* out_round_ms, float* out_fold_ms);
 /* Host utilities, no device needed (like pc_hip_points_sum / pc_hip_point_mul; ipa_pc/mod.rs:672,675 combine a few points on the
  * host): the sum of `count` points; scalar (Montgomery Fr) times one point, the scalar taken as the integer it is. */
 int pc_hip_te_points_sum(pc_te_curve curve, const void* points, size_t count, void* out_xy);

@@ -162,6 +162,14 @@ def load_library():
     lib.pc_hip_te_srs_bytes_resident.argtypes = [vp, C.POINTER(sz)]
     lib.pc_hip_te_msm.argtypes = [vp, vp, sz, vp, ip, ip, sz, vp, C.POINTER(ip)]
     lib.pc_hip_te_ec_fold.argtypes = [vp, vp, sz, vp]
+    lib.pc_hip_te_ec_fold_from.argtypes = [vp, vp, sz, vp, C.POINTER(vp)]
+    lib.pc_hip_te_srs_precompute_fold.argtypes = [vp, vp]
+    lib.pc_hip_te_srs_fold_table_info.argtypes = [vp, C.POINTER(C.c_uint)]
+    lib.pc_hip_te_srs_in_subgroup.argtypes = [vp, vp, C.POINTER(ip)]
+    lib.pc_hip_te_fr_powers.argtypes = [vp, ip, vp, sz, vp]
+    lib.pc_hip_te_ipa_fold_dots.argtypes = [vp, ip, vp, vp, sz, vp, vp, vp]
+    lib.pc_hip_te_ipa_key_scalars.argtypes = [vp, ip, vp, sz, vp, sz, vp, sz, vp, vp]
+    lib.pc_hip_te_ipa_open_rounds.argtypes = [vp, vp, vp, sz, vp, vp, IPA_CHALLENGE_FN, vp, sz, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.pc_hip_te_points_sum.argtypes = [ip, vp, sz, vp]
     lib.pc_hip_te_point_mul.argtypes = [ip, vp, vp, vp]
     lib.pc_hip_ml_fold.argtypes = [vp, ip, vp, sz, vp, vp, vp]
@@ -577,6 +585,30 @@ class Context:
     def upload_te_srs(self, curve, bases, n=None, stride_bytes=0):
         """A resident key of twisted Edwards points (pc_hip_te_srs_upload); curve: a name of TE_CURVES, bases: n x 64 bytes x || y."""
         return TeSrs(self, curve, bases, n, stride_bytes)
+
+    def te_fr_powers(self, curve, z_mont, n, out_dev):
+        """out_dev[i] = z^i, i < n, over the scalar field of a twisted Edwards curve (pc_hip_te_fr_powers); z_mont: 32 bytes, host."""
+        z = np.ascontiguousarray(z_mont)
+        self.check(self.lib.pc_hip_te_fr_powers(self.h, TE_CURVES[curve], C.c_void_p(z.ctypes.data), n, _ptr(out_dev)[0]))
+
+    def te_ipa_fold_dots(self, curve, coeffs_dev, z_dev, m, u=None, u_inv=None):
+        """pc_hip_te_ipa_fold_dots: optional fold at size 2m by (u, u^-1), then the round's two inner products at size m -> (2, 32) uint8."""
+        out = np.zeros((2, 32), dtype=np.uint8)
+        pu = pi = None
+        if u is not None:
+            u, u_inv = np.ascontiguousarray(u), np.ascontiguousarray(u_inv)
+            pu, pi = C.c_void_p(u.ctypes.data), C.c_void_p(u_inv.ctypes.data)
+        self.check(self.lib.pc_hip_te_ipa_fold_dots(self.h, TE_CURVES[curve], _ptr(coeffs_dev)[0], _ptr(z_dev)[0], m, pu, pi, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def te_ipa_key_scalars(self, curve, coeffs_dev, m, s_dev, n0, fold_u=None, fold_m=0, out_l_dev=None, out_r_dev=None):
+        """pc_hip_te_ipa_key_scalars: fold the key factors s by fold_u (optional), build the round's MSM scalars (optional)."""
+        fu = None
+        if fold_u is not None:
+            fold_u = np.ascontiguousarray(fold_u)
+            fu = C.c_void_p(fold_u.ctypes.data)
+        opt = lambda x: None if x is None else _ptr(x)[0]
+        self.check(self.lib.pc_hip_te_ipa_key_scalars(self.h, TE_CURVES[curve], opt(coeffs_dev), m, _ptr(s_dev)[0], n0, fu, fold_m, opt(out_l_dev), opt(out_r_dev)))
 
     def ml_fold(self, curve, r_in_dev, n_half, z, r_out_dev, q_dev):
         """One halving round of MultilinearPC::open on device vectors (pc_hip_ml_fold); z: one Montgomery Fr (host)."""
@@ -1078,6 +1110,13 @@ class TeSrs:
         ctx.check(ctx.lib.pc_hip_te_srs_upload(ctx.h, TE_CURVES[curve], p, n, stride_bytes, where, C.byref(h)))
         self.h, self.n = h, n
 
+    @classmethod
+    def _adopt(cls, ctx, curve, h, n):
+        """a key object the library made (pc_hip_te_ec_fold_from)"""
+        k = cls.__new__(cls)
+        k.ctx, k.curve, k.h, k.n = ctx, curve, h, n
+        return k
+
     def free(self):
         if self.h:
             self.ctx.lib.pc_hip_te_srs_free(self.h)
@@ -1112,6 +1151,66 @@ class TeSrs:
         """key[i] = key[i] + u * key[n_half + i], i < n_half, in place (pc_hip_te_ec_fold); u_mont: one Montgomery Fr (host, 32 bytes)."""
         u_mont = np.ascontiguousarray(u_mont)
         self.ctx.check(self.ctx.lib.pc_hip_te_ec_fold(self.ctx.h, self.h, n_half, C.c_void_p(u_mont.ctypes.data)))
+
+    def ec_fold_from(self, n_half, u_mont):
+        """A new resident key out[i] = key[i] + u * key[n_half + i], i < n_half; this key is untouched (pc_hip_te_ec_fold_from).  From the
+        fold table when this key has one and n_half is half its length, by the ladder otherwise: the same points."""
+        u_mont = np.ascontiguousarray(u_mont)
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pc_hip_te_ec_fold_from(self.ctx.h, self.h, n_half, C.c_void_p(u_mont.ctypes.data), C.byref(h)))
+        return TeSrs._adopt(self.ctx, self.curve, h, n_half)
+
+    def precompute_fold(self):
+        """Fold table of this (committer) key, once per key: 253 rows of its upper half and their doublings (pc_hip_te_srs_precompute_fold)."""
+        self.ctx.check(self.ctx.lib.pc_hip_te_srs_precompute_fold(self.ctx.h, self.h))
+        return self
+
+    def fold_table_info(self):
+        """rows of the fold table on this key; 0: none"""
+        rows = C.c_uint()
+        self.ctx.check(self.ctx.lib.pc_hip_te_srs_fold_table_info(self.h, C.byref(rows)))
+        return rows.value
+
+    def in_subgroup(self):
+        """True if every point of the key lies in the prime-order subgroup (pc_hip_te_srs_in_subgroup; cached on the key)."""
+        out = C.c_int(0)
+        self.ctx.check(self.ctx.lib.pc_hip_te_srs_in_subgroup(self.ctx.h, self.h, C.byref(out)))
+        return bool(out.value)
+
+    def ipa_open_rounds(self, coeffs_dev, n, point_mont, h_prime_xy, next_challenge, fixed_key_below=0, want_times=False):
+        """The whole halving loop of InnerProductArgPC::open on this resident committer key (pc_hip_te_ipa_open_rounds).
+        next_challenge(l_xy, r_xy) (64 bytes each) -> u as 32 Montgomery bytes.  Returns (l_vec, r_vec, final_key, c[, round_ms, fold_ms])."""
+        lg = n.bit_length() - 1
+        pb = TE_POINT_BYTES[self.curve]
+        l = np.zeros((max(lg, 1), pb), dtype=np.uint8)
+        r = np.zeros((max(lg, 1), pb), dtype=np.uint8)
+        fk, c = np.zeros(pb, dtype=np.uint8), np.zeros(32, dtype=np.uint8)
+        err = []
+
+        def cb(_user, lp, rp, up):
+            try:
+                lxy = np.frombuffer((C.c_uint8 * pb).from_address(lp), dtype=np.uint8).copy()
+                rxy = np.frombuffer((C.c_uint8 * pb).from_address(rp), dtype=np.uint8).copy()
+                u = np.ascontiguousarray(next_challenge(lxy, rxy), dtype=np.uint8)
+                assert u.nbytes == 32
+                C.memmove(up, u.ctypes.data, 32)
+            except BaseException as e:      # an exception must not cross the C frames: finish the loop on a dummy challenge, raise afterwards
+                err.append(e)
+                C.memset(up, 0, 32); C.memset(up, 1, 1)
+        fn = IPA_CHALLENGE_FN(cb)
+        point = np.ascontiguousarray(point_mont)
+        hp = np.ascontiguousarray(h_prime_xy)
+        rms = (C.c_float * max(lg, 1))()
+        fms = (C.c_float * max(lg, 1))()
+        p, _ = _ptr(coeffs_dev)
+        rc = self.ctx.lib.pc_hip_te_ipa_open_rounds(self.ctx.h, self.h, p, n, C.c_void_p(point.ctypes.data), C.c_void_p(hp.ctypes.data), fn, None,
+                                                    fixed_key_below, C.c_void_p(l.ctypes.data), C.c_void_p(r.ctypes.data), C.c_void_p(fk.ctypes.data),
+                                                    C.c_void_p(c.ctypes.data), rms, fms)
+        if err:
+            raise err[0]
+        self.ctx.check(rc)
+        out = (l[:lg], r[:lg], fk, c)
+        return out + (list(rms)[:lg], list(fms)[:lg]) if want_times else out
 
 
 def te_points_sum(curve, points):

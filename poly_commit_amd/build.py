@@ -13,7 +13,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["abi_ctx.hip", "abi_srs.hip", "abi_msm.hip", "abi_poly.hip", "abi_ipa.hip", "abi_lincode.hip", "abi_g2.hip", "abi_te.hip", "abi_skzg.hip", "abi_pst13.hip", "group.hip", "hash_tu.hip",
+SOURCES = ["abi_ctx.hip", "abi_srs.hip", "abi_msm.hip", "abi_poly.hip", "abi_ipa.hip", "abi_lincode.hip", "abi_g2.hip", "abi_te.hip", "abi_te_ipa.hip", "abi_skzg.hip", "abi_pst13.hip", "group.hip", "hash_tu.hip",
            "curve_bls12_381.hip", "curve_bn254.hip", "curve_pallas.hip", "curve_bls12_377.hip",
            "field_bls12_381.hip", "field_bn254.hip", "field_pallas.hip", "field_bls12_377.hip"]
 # PC_HIP_VARIANT=name builds an alternative library libpc_hip_<name>.so (own object cache) from the same sources with

@@ -29,6 +29,16 @@ struct Staged {
   ~Staged() { if (owned) be.free(dev); }
 };
 
+// The vectors of an opening's rounds (pc_hip_ipa_open_rounds, pc_hip_te_ipa_open_rounds): the context's grow-only buffers -- 0: the
+// powers of z, 1: the per-base factors of the fixed key, 2: the two scalar vectors of its rounds.  Call inside guarded().
+inline void* ipa_buffer(pc_ctx* ctx, int i, size_t bytes) {
+  if (bytes > ctx->ipa_bytes[i]) {
+    if (ctx->ipa_buf[i]) { ctx->be.sync(); ctx->be.free(ctx->ipa_buf[i]); ctx->ipa_buf[i] = nullptr; ctx->ipa_bytes[i] = 0; }
+    ctx->ipa_buf[i] = ctx->be.alloc(bytes); ctx->ipa_bytes[i] = bytes;
+  }
+  return ctx->ipa_buf[i];
+}
+
 // pc_hip_shutdown's share of the Brakedown code objects (abi_lincode.hip): their device memory goes, a code its caller still holds
 // stays behind as a tombstone that pc_hip_brakedown_code_free only deletes
 void lincodes_shutdown(pc_ctx* ctx);

@@ -150,13 +150,6 @@ static bool ipa_fixed_table() {      // PC_HIP_IPA_FIXED_TABLE=0: the late round
   static const bool on = []() { const char* e = getenv("PC_HIP_IPA_FIXED_TABLE"); return !(e && !strcmp(e, "0")); }();
   return on;
 }
-static void* ipa_buffer(pc_ctx* ctx, int i, size_t bytes) {
-  if (bytes > ctx->ipa_bytes[i]) {
-    if (ctx->ipa_buf[i]) { ctx->be.sync(); ctx->be.free(ctx->ipa_buf[i]); ctx->ipa_buf[i] = nullptr; ctx->ipa_bytes[i] = 0; }
-    ctx->ipa_buf[i] = ctx->be.alloc(bytes); ctx->ipa_bytes[i] = bytes;
-  }
-  return ctx->ipa_buf[i];
-}
 int pc_hip_ipa_open_rounds(pc_ctx* ctx, const pc_srs* comm_key, void* coeffs_dev, size_t n, const void* point_host, const void* h_prime_xy_host,
                            pc_ipa_challenge_fn next_challenge, void* user, size_t fixed_key_below,
                            void* out_l_vec_xy, void* out_r_vec_xy, void* out_final_key_xy, void* out_c_host, float* out_round_ms, float* out_fold_ms) {

@@ -150,6 +150,8 @@ int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* k, size_t n_half, const void* u_ho
   return guarded(ctx, [&]() {
     if (!n_half) return (int)PC_OK;
     pc::HipBackend& be = ctx->be;
+    te_drop_fold_table(k);       // the key changes: its fold table is stale, and what was known about its points
+    k->in_subgroup = -1;
     // the sums in extended coordinates, then the prefix products of the normalisation
     uint32_t* ext = (uint32_t*)be.workspace(n_half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);
     uint32_t* scratch = ext + n_half * (size_t)pc::TE_XW;
@@ -161,6 +163,101 @@ int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* k, size_t n_half, const void* u_ho
     pc::TeBatchAffineBody<TeC> nb{ext, scratch, k->bases, (uint32_t)n_half, pc::TE_NORM_K};
     be.launch(nb, (n_half + pc::TE_NORM_K - 1) / pc::TE_NORM_K);
     be.sync();
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_te_ec_fold_from(pc_ctx* ctx, const pc_te_srs* src, size_t n_half, const void* u_host, pc_te_srs** out) {
+  if (!ctx || !src || src->ctx != ctx || !u_host || !out || !n_half || 2 * n_half > src->n) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  *out = nullptr;
+  pc_te_srs* dst = nullptr;
+  int rc = guarded(ctx, [&]() {
+    dst = te_key_create(ctx, src->te_curve, n_half, (size_t)TE_AW * 4);
+    if (!dst) return (int)PC_ERR_OOM;
+    pc::HipBackend& be = ctx->be;
+    uint32_t* ext = (uint32_t*)be.workspace(n_half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);
+    uint32_t* scratch = ext + n_half * (size_t)pc::TE_XW;
+    pc::NafMasks<pc::TE_FR_W> naf;
+    naf.from_scalar(pc::Fd<pc::TeFrP>::load((const uint32_t*)u_host).from_mont().l);
+    // from the key's table when it has one for this half and every digit of u has a row; the ladder otherwise: the same points
+    pc::TeTableFoldBody<TeC> t;
+    if (src->fold_tbl && 2 * n_half == src->n && t.dg.from_naf(naf, src->fold_rows)) {
+      t.key = src->bases; t.tbl = src->fold_tbl; t.half = (uint32_t)n_half; t.ext = ext;
+      be.launch(t, n_half);
+    } else {
+      pc::TeEcFoldBody<TeC> f;
+      f.key = src->bases; f.half = (uint32_t)n_half; f.ext = ext; f.naf = naf;
+      be.launch(f, n_half);
+    }
+    pc::TeBatchAffineBody<TeC> nb{ext, scratch, dst->bases, (uint32_t)n_half, pc::TE_NORM_K};
+    be.launch(nb, (n_half + pc::TE_NORM_K - 1) / pc::TE_NORM_K);
+    be.sync();
+    if (src->in_subgroup == 1) dst->in_subgroup = 1;      // sums of multiples of subgroup points
+    return (int)PC_OK;
+  });
+  if (rc != PC_OK) { if (dst) te_key_free(dst); return rc; }
+  *out = dst;
+  return PC_OK;
+}
+
+int pc_hip_te_srs_precompute_fold(pc_ctx* ctx, pc_te_srs* k) {
+  if (!ctx || !k || k->ctx != ctx || k->n < 2 || (k->n & 1)) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    te_drop_fold_table(k);
+    pc::HipBackend& be = ctx->be;
+    const size_t half = k->n / 2, row_words = half * (size_t)TE_AW, need = (size_t)pc::TE_FOLD_ROWS * row_words * 4;
+    // refused above the share of the device's FREE memory that pc_hip_srs_precompute_fold allows (the same knob); folds then run the ladder
+    static const double frac = []() { const char* e = getenv("PC_HIP_FOLD_TABLE_MAX_FRAC"); double v = e ? atof(e) : 0.5; return v < 0 ? 0.0 : v > 1 ? 1.0 : v; }();
+    size_t free_b = 0, total_b = 0;
+    PC_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    if ((double)need > frac * (double)free_b) {
+      ctx->last_error = "fold table of " + std::to_string(need >> 20) + " MiB exceeds the allowed share of the free device memory";
+      return (int)PC_ERR_UNSUPPORTED;
+    }
+    uint32_t* ext = (uint32_t*)be.workspace(half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);
+    uint32_t* scratch = ext + half * (size_t)pc::TE_XW;
+    uint32_t* tbl = (uint32_t*)be.alloc(need);
+    try {
+      be.copy_d2d(tbl, k->bases + row_words, row_words * 4);      // row 0: the upper half as it is
+      for (uint32_t b = 0; b + 1 < pc::TE_FOLD_ROWS; b++) {     // row b + 1: one batched doubling of row b, normalised
+        pc::TeDblRowBody<TeC> d{tbl + b * row_words, ext};
+        be.launch(d, half);
+        pc::TeBatchAffineBody<TeC> nb{ext, scratch, tbl + (b + 1) * row_words, (uint32_t)half, pc::TE_NORM_K};
+        be.launch(nb, (half + pc::TE_NORM_K - 1) / pc::TE_NORM_K);
+      }
+      be.sync();
+    } catch (...) { (void)hipStreamSynchronize(be.stream); be.free(tbl); throw; }
+    k->fold_tbl = tbl; k->fold_rows = pc::TE_FOLD_ROWS;
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_te_srs_fold_table_info(const pc_te_srs* k, unsigned* out_rows) {
+  if (!k || !out_rows) return PC_ERR_INVALID_ARG;
+  *out_rows = k->fold_tbl ? k->fold_rows : 0;
+  return PC_OK;
+}
+
+int pc_hip_te_srs_in_subgroup(pc_ctx* ctx, pc_te_srs* k, int* out) {
+  if (!ctx || !k || k->ctx != ctx || !out) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  if (k->in_subgroup >= 0) { *out = k->in_subgroup; return PC_OK; }
+  return guarded(ctx, [&]() {
+    int all = 1;
+    if (k->n) {
+      CallBuf flags(ctx->be, 1, k->n * 4);
+      pc::TeSubgroupBody<TeC> b;
+      b.key = k->bases; b.flags = (uint32_t*)flags.dev;
+      b.naf.from_scalar(pc::TeFrP::MOD);
+      ctx->be.launch(b, k->n);
+      std::vector<uint32_t> h(k->n);
+      ctx->be.copy_d2h(h.data(), flags.dev, k->n * 4);
+      for (uint32_t f : h) all &= (int)(f & 1u);
+    }
+    k->in_subgroup = all;
+    *out = all;
     return (int)PC_OK;
   });
 }

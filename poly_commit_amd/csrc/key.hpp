@@ -533,11 +533,20 @@ struct TeLane {
 struct pc_te_srs : pc_key_base {
   pc_te_curve te_curve = PC_TE_ED_ON_BLS12_381;
   TeLane* lane = nullptr;
+  uint32_t* fold_tbl = nullptr;  // fold table (pc_hip_te_srs_precompute_fold): fold_rows rows of the n / 2 upper points and their doublings, or null
+  uint32_t fold_rows = 0;
+  int in_subgroup = -1;          // pc_hip_te_srs_in_subgroup's cached answer (-1: not asked yet)
 };
+inline void te_drop_fold_table(pc_te_srs* k) {
+  if (k->fold_tbl) k->ctx->be.free(k->fold_tbl);
+  k->fold_tbl = nullptr; k->fold_rows = 0;
+}
+inline size_t te_fold_table_bytes(const pc_te_srs* k) { return k->fold_tbl ? (size_t)k->fold_rows * (k->n / 2) * (size_t)k->aw * 4 : 0; }
 inline void te_key_release_device(pc_te_srs* k) {
   if (!k->ctx) return;
   (void)hipSetDevice(k->ctx->device);
   delete k->lane; k->lane = nullptr;
+  te_drop_fold_table(k);
   key_base_release(k->ctx->te_keys, k);
 }
 inline void te_key_free(pc_te_srs* k) { te_key_release_device(k); delete k; }
@@ -547,9 +556,9 @@ inline pc_te_srs* te_key_create(pc_ctx* ctx, pc_te_curve curve, size_t n, size_t
   if (k) k->te_curve = curve;
   return k;
 }
-// {bases, 0, 0, pipeline} bytes of one key (the layout of key_bytes: no tables)
+// {bases, 0, fold table, pipeline} bytes of one key (the layout of key_bytes: no window tables)
 inline void te_key_bytes(const pc_te_srs* k, size_t out[4]) {
-  out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = out[2] = 0;
+  out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = 0; out[2] = te_fold_table_bytes(k);
   out[3] = k->lane ? k->lane->be.bytes_live : 0;
 }
 inline void te_keys_shutdown(pc_ctx* ctx) { key_registry_shutdown(ctx->te_keys, te_key_release_device); }

@@ -186,6 +186,98 @@ struct TeBatchAffineBody {
   }
 };
 
+// ---- the fold table of a committer key (pc_hip_te_srs_precompute_fold) ------------------------------------------------------
+// T[b][j] = 2^b * key[n/2 + j] for b < TE_FOLD_ROWS, row-major in j, every record in the resident form: the first fold of every
+// opening multiplies the same upper half of the key by that opening's challenge, and with the doublings stored a fold is one mixed
+// addition per non-zero NAF digit (a third of the positions) instead of a doubling per position on top of them.  The curve has no
+// endomorphism: there is no GLV split to halve the rows.  253 = the NAF positions of a 252-bit scalar, carry included.
+static constexpr uint32_t TE_FOLD_ROWS = 253;
+
+// one row from the one below: ext[j] = 2 * in[j], left in extended coordinates for TeBatchAffineBody (an all-zero record stays empty
+// and is normalised to the identity, which the fold adds as it would skip the empty one)
+template <class G>
+struct TeDblRowBody {
+  typedef XyzzD<G> Pt;
+  typedef AffD<G> Aff;
+  const uint32_t* in; uint32_t* ext;
+  PC_HD void operator()(uint32_t j) const {
+    const Aff a = Aff::load(in + (size_t)j * Aff::WORDS);
+    uint32_t* o = ext + (size_t)j * Pt::WORDS;
+    if (a.is_inf()) { for (int w = 0; w < Pt::WORDS; w++) o[w] = 0; return; }
+    Pt p; p.X = a.x; p.Y = a.y; p.Z = Pt::Fq::one(); p.Tc = a.x.mul(a.y);
+    p.dbl().store(o);
+  }
+};
+
+// the non-zero NAF digits of a fold challenge, one entry each: the table row in bits 0..14, bit 15 set for digit -1.  Made once on
+// the host and passed by value: every lane of a wave walks the same list (no divergence, the entries come through the scalar unit).
+struct TeFoldDigits {
+  static constexpr uint32_t MAX = 128;       // a NAF of 253 positions has at most 127 non-zero digits
+  uint32_t count;
+  uint16_t d[MAX];
+  // false: a digit at or above `rows` (the caller runs the ladder)
+  template <int NW>
+  bool from_naf(const NafMasks<NW>& naf, uint32_t rows) {
+    count = 0;
+    for (uint32_t bit = 0; bit < 32u * (NW + 1); bit++) {
+      const uint32_t w = bit >> 5, m = 1u << (bit & 31);
+      if (!((naf.pos[w] | naf.neg[w]) & m)) continue;
+      if (bit >= rows || count >= MAX) return false;
+      d[count++] = (uint16_t)(bit | ((naf.neg[w] & m) ? 0x8000u : 0u));
+    }
+    return true;
+  }
+};
+
+// ext[i] = key[i] + sum over the digits of +-T[row][i]: the same integer combination as TeEcFoldBody's ladder (exact for operands of any
+// order; nothing uses r P = O), so the normalised result is the same, bit for bit.  The next row's record is loaded while the current
+// addition runs (as the accumulate's StageRegs does for its next base): consecutive lanes read consecutive 96-byte records of one
+// row.  u = 0: no digits, key[i] itself; an all-zero record counts as the identity.
+template <class G>
+struct TeTableFoldBody {
+  typedef XyzzD<G> Pt;
+  typedef AffD<G> Aff;
+  const uint32_t* key; const uint32_t* tbl; uint32_t half;
+  uint32_t* ext;           // half x Pt::WORDS
+  TeFoldDigits dg;
+  PC_HD void operator()(uint32_t i) const {
+    Pt acc = Pt::from_affine(Aff::load(key + (size_t)i * Aff::WORDS));
+    const uint32_t* col = tbl + (size_t)i * Aff::WORDS;
+    const size_t row = (size_t)half * Aff::WORDS;
+    Aff nxt = dg.count ? Aff::load(col + (size_t)(dg.d[0] & 0x7fffu) * row) : Aff::infinity();
+    for (uint32_t k = 0; k < dg.count; k++) {
+      const Aff cur = nxt.neg_if((dg.d[k] >> 15) != 0);
+      if (k + 1 < dg.count) nxt = Aff::load(col + (size_t)(dg.d[k + 1] & 0x7fffu) * row);
+      acc.add_affine(cur);
+    }
+    if (acc.is_inf()) acc = Pt::identity();
+    acc.store(ext + (size_t)i * Pt::WORDS);
+  }
+};
+
+// flags[i] = 1 if r * key[i] is the identity (key[i] lies in the prime-order subgroup), else 0: the NAF ladder of the group order r,
+// its masks made on the host.  The fixed-key rounds of an opening reduce products of challenges modulo r before they meet a base,
+// which is exact only for such points; the ABI itself takes any curve point.  An all-zero entry counts as the identity.
+template <class G>
+struct TeSubgroupBody {
+  typedef XyzzD<G> Pt;
+  typedef AffD<G> Aff;
+  static constexpr int NW = G::FrP::N;
+  const uint32_t* key; uint32_t* flags;
+  NafMasks<NW> naf;        // of r
+  PC_HD void operator()(uint32_t i) const {
+    const Aff p = Aff::load(key + (size_t)i * Aff::WORDS), np = p.neg_if(true);
+    Pt acc = Pt::infinity();
+    for (int bit = 32 * (NW + 1) - 1; bit >= 0; bit--) {
+      const uint32_t w = bit >> 5, m = 1u << (bit & 31);
+      if (!acc.is_inf()) acc = acc.dbl(); else if (!((naf.pos[w] | naf.neg[w]) & m)) continue;
+      if (naf.pos[w] & m) acc.add_affine(p); else if (naf.neg[w] & m) acc.add_affine(np);
+    }
+    // the identity is X = 0 and Y = Z ((0, -1) of order 2 has X = 0 too)
+    flags[i] = (acc.is_inf() || (acc.X.is_zero() && acc.Y.sub(acc.Z).is_zero())) ? 1u : 0u;
+  }
+};
+
 // ---- the host side (64-bit limbs): the MSM's Horner tail and the handful-of-points utilities --------------------------------
 namespace host64 {
 template <class T>

@@ -17,6 +17,9 @@
 //                     [round 2 had the 0x80 condition inverted; the BN254 generator (1, 2) must end in 0x00, its negation in 0x80]
 //   BLS12-381 G1      zcash / IETF encoding: x, y big-endian 48 bytes each; byte 0: 0x80 compressed (clear), 0x40 infinity
 //   from_random_bytes the first 8 N bytes little-endian, bits above MODULUS_BIT_SIZE cleared, None if >= modulus
+//   TE affine point   (ed_on_bls12_381; used by poly_commit_amd/te_ipa.py, no C++ mirror yet) generic twisted_edwards impl, uncompressed:
+//                     x, then y, each a canonical little-endian residue in 32 bytes, NO flag bits; its 252-bit scalar field's
+//                     from_random_bytes clears the top 4 bits of the 32 bytes and answers None at >= r.  As unconfirmed as the rest.
 // This is a handful of hashes of < 200 bytes per round: host work, exactly where the reference does it.
 #pragma once
 #include <stdint.h>

@@ -40,6 +40,9 @@ GROUPS = [
     ("InnerProductArgPC over the twisted Edwards curve ed_on_bls12_381, the reference's own instantiation (ipa_pc/mod.rs:1056-1064): cm_commit's msm_bigint (:54-72), the key fold of open (:699-707), the key's residency (trim, :359-401)",
      ["pc_hip_te_srs_upload", "pc_hip_te_srs_free", "pc_hip_te_srs_len", "pc_hip_te_srs_read", "pc_hip_te_srs_bytes_resident", "pc_hip_te_msm", "pc_hip_te_ec_fold",
       "pc_hip_te_points_sum", "pc_hip_te_point_mul"]),
+    ("InnerProductArgPC::open over ed_on_bls12_381 on the device: the vectors of the halving rounds over the 252-bit scalar field (ipa_pc/mod.rs:641-649, 672-697), the out-of-place key fold and its table (:699-707), the subgroup fact that sample_generators establishes (:320), the rounds as one call (:664-711)",
+     ["pc_hip_te_fr_powers", "pc_hip_te_ipa_fold_dots", "pc_hip_te_ipa_key_scalars", "pc_hip_te_ec_fold_from", "pc_hip_te_srs_precompute_fold", "pc_hip_te_srs_fold_table_info",
+      "pc_hip_te_srs_in_subgroup", "pc_hip_te_ipa_open_rounds"]),
     ("one committer key over the GPUs of a node, one process",
      ["pc_hip_group_create", "pc_hip_group_destroy", "pc_hip_group_size", "pc_hip_group_ctx", "pc_hip_group_srs_upload", "pc_hip_group_srs_free",
       "pc_hip_group_srs_len", "pc_hip_group_msm", "pc_hip_group_msm_batch", "pc_hip_group_kzg_open", "pc_hip_group_commit_open_async", "pc_hip_group_job_wait", "pc_hip_group_ntt_batch", "pc_hip_group_ligero_commit"]),
