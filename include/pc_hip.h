@@ -44,7 +44,8 @@ typedef enum {
   PC_ERR_HIP = -3,
   PC_ERR_NO_DEVICE = -4,
   PC_ERR_TOO_LARGE = -5,
-  PC_ERR_UNSUPPORTED = -6
+  PC_ERR_UNSUPPORTED = -6,
+  PC_ERR_INTERNAL = -7
 } pc_status;
 
 /* Library / device lifetime. */
@@ -788,7 +789,7 @@ int pc_hip_te_srs_fold_table_info(const pc_te_srs* srs, unsigned* out_rows);
 /* *out = 1 if every point of the key lies in the prime-order subgroup (r * P is the identity; an all-zero entry counts as the
  * identity), else 0.  One ladder per point the first time, then the cached answer.  The fixed-key rounds of pc_hip_te_ipa_open_rounds
  * multiply scalars modulo r before they meet a base, which is exact only on such a key; sample_generators makes such keys
- * (mul_by_cofactor_to_group, ipa_pc/mod.rs:320), the ABI does not require them. */
+ * (mul_by_cofactor_to_group, ipa_pc/mod.rs:320; pc_hip_te_sample_generators), the ABI does not require them. */
 int pc_hip_te_srs_in_subgroup(pc_ctx* ctx, pc_te_srs* srs, int* out);
 /* The vector kernels of the halving rounds over the curve's scalar field: contracts, argument checks and error codes of
  * pc_hip_fr_powers, pc_hip_ipa_fold_dots and pc_hip_ipa_key_scalars, with a pc_te_curve where those take the pc_curve of the field. */
@@ -811,6 +812,22 @@ int pc_hip_te_ipa_open_rounds(pc_ctx* ctx, const pc_te_srs* comm_key, void* coef
  * host): the sum of `count` points; scalar (Montgomery Fr) times one point, the scalar taken as the integer it is. */
 int pc_hip_te_points_sum(pc_te_curve curve, const void* points, size_t count, void* out_xy);
 int pc_hip_te_point_mul(pc_te_curve curve, const void* point, const void* scalar_mont, void* out_xy);
+/* InnerProductArgPC::sample_generators (ipa_pc/mod.rs:302-325) with D = Blake2s256: generators [first_index, first_index + count) as a
+ * NEW resident key (the caller frees it), made on the device, one lane per index -- generator i is 8 * from_random_bytes(D(name ||
+ * le64(i))), or while that is None, for j = 0, 1, ..., 8 * from_random_bytes(D(name || le64(i) || le64(j))); then normalize_batch.
+ * setup (:344-366) is this call with first_index = 0 and count = max_degree + 3.  protocol_name: name_len <= 48 bytes on the host (may
+ * be null at 0), the reference's is "PC-DL-2020".  out_digests_host (optional, count entries): the digests index first_index + k
+ * consumed (1: the first one was accepted).  The points lie in the prime-order subgroup by construction (8 * P in a group of order
+ * 8 r): pc_hip_te_srs_in_subgroup answers 1 without a ladder.  twisted_edwards::Affine::from_random_bytes is restated from ark-ec 0.5
+ * (csrc/te_setup.hpp) and NOT confirmed against the crate.  count == 0, name_len > 48, first_index + count beyond 64 bits, any curve
+ * id but PC_TE_ED_ON_BLS12_381: PC_ERR_INVALID_ARG; count >= 2^31: PC_ERR_TOO_LARGE.  A lane's retry loop is capped at 256 digests
+ * (a rejection has probability about 0.55): PC_ERR_INTERNAL, and no key, if one ever hits the cap. */
+int pc_hip_te_sample_generators(pc_ctx* ctx, pc_te_curve curve, const void* protocol_name, size_t name_len, uint64_t first_index,
+                                size_t count, uint32_t* out_digests_host, pc_te_srs** out);
+/* trim's comm_key[0..count) (ipa_pc/mod.rs:384): a NEW resident key of the first `count` points of src, a device copy (the caller
+ * frees it); src is untouched.  What is known about src's subgroup membership carries over when it is 1; the new key has no fold table.
+ * count == 0 or beyond the key: PC_ERR_INVALID_ARG. */
+int pc_hip_te_srs_prefix(pc_ctx* ctx, const pc_te_srs* src, size_t count, pc_te_srs** out);
 
 #ifdef __cplusplus
 }

@@ -172,6 +172,8 @@ def load_library():
     lib.pc_hip_te_ipa_open_rounds.argtypes = [vp, vp, vp, sz, vp, vp, IPA_CHALLENGE_FN, vp, sz, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.pc_hip_te_points_sum.argtypes = [ip, vp, sz, vp]
     lib.pc_hip_te_point_mul.argtypes = [ip, vp, vp, vp]
+    lib.pc_hip_te_sample_generators.argtypes = [vp, ip, vp, sz, C.c_uint64, sz, C.POINTER(C.c_uint32), C.POINTER(vp)]
+    lib.pc_hip_te_srs_prefix.argtypes = [vp, vp, sz, C.POINTER(vp)]
     lib.pc_hip_ml_fold.argtypes = [vp, ip, vp, sz, vp, vp, vp]
     lib.pc_hip_ml_open.argtypes = [vp, vp, vp, ip, C.c_uint, vp, vp, C.POINTER(ip)]
     lib.pc_hip_ml_eq_evals.argtypes = [vp, ip, vp, C.c_uint, vp]
@@ -585,6 +587,18 @@ class Context:
     def upload_te_srs(self, curve, bases, n=None, stride_bytes=0):
         """A resident key of twisted Edwards points (pc_hip_te_srs_upload); curve: a name of TE_CURVES, bases: n x 64 bytes x || y."""
         return TeSrs(self, curve, bases, n, stride_bytes)
+
+    def te_sample_generators(self, curve, protocol_name, first_index, count, want_digests=False):
+        """InnerProductArgPC::sample_generators on the device (pc_hip_te_sample_generators): generators [first_index, first_index + count)
+        of the byte string protocol_name (at most 48 bytes) as a new resident TeSrs; with want_digests also the uint32 array of the
+        digests every index consumed (1: the first one was accepted)."""
+        name = bytes(protocol_name)
+        digests = np.zeros(max(count, 1), dtype=np.uint32) if want_digests else None
+        h = C.c_void_p()
+        self.check(self.lib.pc_hip_te_sample_generators(self.h, TE_CURVES[curve], name, len(name), first_index, count,
+                                                        digests.ctypes.data_as(C.POINTER(C.c_uint32)) if want_digests else None, C.byref(h)))
+        key = TeSrs._adopt(self, curve, h, count)
+        return (key, digests[:count]) if want_digests else key
 
     def te_fr_powers(self, curve, z_mont, n, out_dev):
         """out_dev[i] = z^i, i < n, over the scalar field of a twisted Edwards curve (pc_hip_te_fr_powers); z_mont: 32 bytes, host."""
@@ -1159,6 +1173,13 @@ class TeSrs:
         h = C.c_void_p()
         self.ctx.check(self.ctx.lib.pc_hip_te_ec_fold_from(self.ctx.h, self.h, n_half, C.c_void_p(u_mont.ctypes.data), C.byref(h)))
         return TeSrs._adopt(self.ctx, self.curve, h, n_half)
+
+    def prefix(self, count):
+        """A new resident key of the first `count` points, a device copy; this key is untouched (pc_hip_te_srs_prefix): trim's
+        comm_key[0..count)."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pc_hip_te_srs_prefix(self.ctx.h, self.h, count, C.byref(h)))
+        return TeSrs._adopt(self.ctx, self.curve, h, count)
 
     def precompute_fold(self):
         """Fold table of this (committer) key, once per key: 253 rows of its upper half and their doublings (pc_hip_te_srs_precompute_fold)."""

@@ -46,6 +46,7 @@ const char* pc_hip_strerror(int status) {
     case PC_ERR_NO_DEVICE: return "no HIP device";
     case PC_ERR_TOO_LARGE: return "problem too large for this build";
     case PC_ERR_UNSUPPORTED: return "unsupported";
+    case PC_ERR_INTERNAL: return "internal error";
     default: return "unknown status";
   }
 }

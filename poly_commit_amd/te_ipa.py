@@ -9,6 +9,10 @@ to the ones in host/transcript.hpp and, like them, NOT yet confirmed against the
   TE affine point    serialize_uncompressed: x, then y, each a canonical little-endian residue in 32 bytes; no flag bits (the flags of
                      twisted_edwards::Affine belong to the compressed form only)
   from_random_bytes  the 32 bytes little-endian with the top 4 bits cleared (252-bit modulus); None at >= r
+
+setup and trim (ipa_pc/mod.rs:344-400) make the key on the device: sample_generators is one call of the library
+(pc_hip_te_sample_generators), whose from_random_bytes for twisted_edwards::Affine is restated in csrc/te_setup.hpp and, like the
+conventions above, NOT confirmed against the crates.
 """
 import hashlib
 
@@ -55,6 +59,37 @@ def random_oracle_challenge(data):
         if v is not None:
             return fr_from_int(v)
         i += 1
+
+
+PROTOCOL_NAME = b"PC-DL-2020"
+
+
+def _pow2_at_least(n):
+    return 1 if n <= 1 else 1 << (n - 1).bit_length()
+
+
+def setup(ctx, max_degree, protocol_name=PROTOCOL_NAME):
+    """InnerProductArgPC::setup (ipa_pc/mod.rs:344-366): max_degree + 1 is rounded up to a power of two and max_degree + 3 generators
+    are sampled on the device.  Returns the UniversalParams as a dict: comm_key, a resident TeSrs of max_degree + 1 points; s and h,
+    generators max_degree + 1 and max_degree + 2 (the reference pops h first: it is the last one) as 64 host bytes x || y; max_degree."""
+    max_degree = _pow2_at_least(max_degree + 1) - 1
+    gens = ctx.te_sample_generators(CURVE, protocol_name, 0, max_degree + 3)
+    try:
+        tail = gens.read(max_degree + 1, 2)
+        comm_key = gens.prefix(max_degree + 1)
+    finally:
+        gens.free()
+    return dict(comm_key=comm_key, s=tail[0].copy(), h=tail[1].copy(), max_degree=max_degree)
+
+
+def trim(pp, supported_degree):
+    """InnerProductArgPC::trim (ipa_pc/mod.rs:368-400): supported_degree + 1 is rounded up to a power of two; the committer key is the
+    prefix of pp's (a resident key of its own, pp is untouched).  The committer and the verifier key hold the same values: one dict."""
+    supported_degree = _pow2_at_least(supported_degree + 1) - 1
+    if supported_degree > pp["max_degree"]:
+        raise ValueError("TrimmingDegreeTooLarge")
+    return dict(comm_key=pp["comm_key"].prefix(supported_degree + 1), s=pp["s"], h=pp["h"], supported_degree=supported_degree,
+                max_degree=pp["max_degree"])
 
 
 def ipa_open(ctx, comm_key, h_xy, coeffs_dev, comm, point_mont, opening_challenge, fixed_key_below=0, timings=None):

@@ -43,6 +43,8 @@ GROUPS = [
     ("InnerProductArgPC::open over ed_on_bls12_381 on the device: the vectors of the halving rounds over the 252-bit scalar field (ipa_pc/mod.rs:641-649, 672-697), the out-of-place key fold and its table (:699-707), the subgroup fact that sample_generators establishes (:320), the rounds as one call (:664-711)",
      ["pc_hip_te_fr_powers", "pc_hip_te_ipa_fold_dots", "pc_hip_te_ipa_key_scalars", "pc_hip_te_ec_fold_from", "pc_hip_te_srs_precompute_fold", "pc_hip_te_srs_fold_table_info",
       "pc_hip_te_srs_in_subgroup", "pc_hip_te_ipa_open_rounds"]),
+    ("InnerProductArgPC::setup and trim over ed_on_bls12_381 on the device (ipa_pc/mod.rs:302-325, 344-400): sample_generators -- Blake2s, from_random_bytes with its square root, the cofactor, normalize_batch -- as a new resident key, and trim's prefix of it",
+     ["pc_hip_te_sample_generators", "pc_hip_te_srs_prefix"]),
     ("one committer key over the GPUs of a node, one process",
      ["pc_hip_group_create", "pc_hip_group_destroy", "pc_hip_group_size", "pc_hip_group_ctx", "pc_hip_group_srs_upload", "pc_hip_group_srs_free",
       "pc_hip_group_srs_len", "pc_hip_group_msm", "pc_hip_group_msm_batch", "pc_hip_group_kzg_open", "pc_hip_group_commit_open_async", "pc_hip_group_job_wait", "pc_hip_group_ntt_batch", "pc_hip_group_ligero_commit"]),
@@ -82,7 +84,7 @@ def main():
                            ["PC_SCALARS_CANONICAL", "PC_SCALARS_MONTGOMERY"]))
     out.append(const_block("pc_mem", ["PC_MEM_HOST", "PC_MEM_DEVICE"]))
     out.append(const_block("pc_hash", ["PC_HASH_SHA256", "PC_HASH_BLAKE2S"]))
-    out.append(const_block("pc_status", ["PC_OK", "PC_ERR_INVALID_ARG", "PC_ERR_OOM", "PC_ERR_HIP", "PC_ERR_NO_DEVICE", "PC_ERR_TOO_LARGE", "PC_ERR_UNSUPPORTED"]))
+    out.append(const_block("pc_status", ["PC_OK", "PC_ERR_INVALID_ARG", "PC_ERR_OOM", "PC_ERR_HIP", "PC_ERR_NO_DEVICE", "PC_ERR_TOO_LARGE", "PC_ERR_UNSUPPORTED", "PC_ERR_INTERNAL"]))
     out.append(const_block("limits", sorted(defs)))
     out.append('#[link(name = "pc_hip")]\nextern "C" {')
     for title, names in GROUPS:

@@ -24,6 +24,10 @@ A = Q - 1
 D = (-10240 * pow(10241, -1, Q)) % Q
 GX = 8076246640662884909881801758704306714034609987455869804520522091855516602923
 GY = 13262374693698910701929044844600465831413122818447359594527400194675274060458
+SQRT_S = 32                                  # the 2-adicity of q - 1
+SQRT_T = (Q - 1) >> SQRT_S
+SQRT_Z = 5                                   # the least non-square of Fq
+SQRT_C = pow(SQRT_Z, SQRT_T, Q)
 
 
 def on_curve(p):
@@ -91,6 +95,13 @@ def check_facts():
     x2 = (1 - y * y) * pow(A - D * y * y, -1, Q) % Q
     t8 = mul(R, (sqrt_mod(x2), y))
     assert on_curve(t8) and mul(4, t8) == (0, Q - 1) and mul(8, t8) == (0, 1)
+    # the square root in Fq (csrc/te_setup.hpp): q - 1 = 2^32 t with t odd, c = z^t of order exactly 2^32 for the non-square z,
+    # and a / d a non-square, so that the denominator a - d y^2 of the decompression is never zero
+    assert SQRT_T % 2 == 1 and Q - 1 == SQRT_T << SQRT_S
+    assert pow(SQRT_Z, (Q - 1) // 2, Q) == Q - 1
+    assert pow(SQRT_C, 1 << (SQRT_S - 1), Q) == Q - 1 and pow(SQRT_C, 1 << SQRT_S, Q) == 1
+    assert ((SQRT_T - 1) // 2).bit_length() <= 32 * 7
+    assert pow(A * pow(D, -1, Q) % Q, (Q - 1) // 2, Q) == Q - 1
 
 
 def sqrt_mod(v):
@@ -148,6 +159,11 @@ def render():
           f"  static constexpr uint32_t D2[{n}] = {fmt(2 * D * qm % Q)};   // 2 d, Montgomery",
           f"  static constexpr uint32_t GX[{n}] = {fmt(GX * qm % Q)};  // generator, Montgomery",
           f"  static constexpr uint32_t GY[{n}] = {fmt(GY * qm % Q)};",
+          "  // the square root in Fq (te_setup.hpp): q - 1 = 2^SQRT_S * t, SQRT_EXP = (t - 1) / 2, SQRT_C = z^t of order 2^SQRT_S (z = 5), Montgomery",
+          f"  static constexpr int SQRT_S = {SQRT_S};",
+          "  static constexpr int SQRT_EXP_WORDS = 7;",
+          f"  static constexpr uint32_t SQRT_EXP[7] = {fmt((SQRT_T - 1) // 2, 7)};",
+          f"  static constexpr uint32_t SQRT_C[{n}] = {fmt(SQRT_C * qm % Q)};",
           '  static constexpr const char* NAME = "ed_on_bls12_381";',
           "};", ""]
     return "\n".join(o)
