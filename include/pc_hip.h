@@ -181,7 +181,8 @@ int pc_hip_last_msm_phases_ms(const pc_ctx* ctx, float out[8]);
  * take the UNION of the accumulate intervals [out[3], out[4]] of a timed region (bench.py's roofline.kernel_ms). */
 int pc_hip_last_msm_marks_ms(const pc_ctx* ctx, float out[8]);
 /* Geometry the last completed MSM ran with: {window bits c, signed digits per scalar (= mixed additions per pair),
- * buckets, 1 if the window table was used}.  For bench.py's arithmetic roofline. */
+ * buckets, 1 if the window table was used}.  For bench.py's arithmetic roofline.  pc_hip_g2_msm and pc_hip_te_msm of at least one
+ * pair record theirs too (out[3] = 0: both pipelines are table-free); the MSMs inside pc_hip_ml_open do not. */
 int pc_hip_last_msm_shape(const pc_ctx* ctx, uint32_t out[4]);
 
 

@@ -24,6 +24,10 @@ struct G2RunnerT : G2Runner {
     if (where == PC_MEM_HOST && n) { be.copy_h2d(plan.scalar_staging(), scalars, n * (size_t)FR_W * 4); sdev = plan.scalar_staging(); }
     plan.run(bases, base_off, sdev, n, from_mont, out_host);
   }
+  void shape(uint32_t out[4]) const override {
+    const MsmGeom& g = plan.last_geom();
+    out[0] = g.c; out[1] = g.Wd; out[2] = g.NB; out[3] = 0;
+  }
 };
 
 G2Lane* g2_lane(pc_g2_srs* k) {
@@ -263,6 +267,7 @@ int pc_hip_g2_msm(pc_ctx* ctx, const pc_g2_srs* kc, size_t base_offset, const vo
     G2Lane* L = pc::g2_lane(k);
     L->be.timing = ctx->be.timing;
     L->runner->run(k->bases, (uint32_t)base_offset, scalars, where, n, form == PC_SCALARS_MONTGOMERY, (uint32_t*)out_xy);
+    if (n) L->runner->shape(ctx->shape);      // (pc_hip_last_msm_shape; an empty call plans nothing)
     if (out_is_infinity) *out_is_infinity = affine_is_zero((const uint32_t*)out_xy, G2_AW);
     return (int)PC_OK;
   });

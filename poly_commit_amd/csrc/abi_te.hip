@@ -26,6 +26,10 @@ struct TeRunnerT : TeRunner {
     if (where == PC_MEM_HOST) { be.copy_h2d(plan.scalar_staging(), scalars, n * (size_t)TE_FR_W * 4); sdev = plan.scalar_staging(); }
     plan.run(bases, base_off, sdev, n, from_mont, out_host);
   }
+  void shape(uint32_t out[4]) const override {
+    const MsmGeom& g = plan.last_geom();
+    out[0] = g.c; out[1] = g.Wd; out[2] = g.NB; out[3] = 0;
+  }
 };
 
 TeLane* te_lane(pc_te_srs* k) {
@@ -136,6 +140,7 @@ int pc_hip_te_msm(pc_ctx* ctx, const pc_te_srs* kc, size_t base_offset, const vo
     TeLane* L = pc::te_lane(k);
     L->be.timing = ctx->be.timing;
     L->runner->run(k->bases, (uint32_t)base_offset, scalars, where, n, form == PC_SCALARS_MONTGOMERY, (uint32_t*)out_xy);
+    L->runner->shape(ctx->shape);      // (pc_hip_last_msm_shape)
     if (out_is_identity) *out_is_identity = pc::host64::te_is_identity<pc_te_ed_on_bls12_381>((const uint32_t*)out_xy) ? 1 : 0;
     // phase brackets of the call (pc_hip_last_msm_phases_ms), as for a G1 pipeline
     for (int i = 0; i < 8; i++) ctx->phases[i] = 0;

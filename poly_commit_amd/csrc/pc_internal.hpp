@@ -52,6 +52,8 @@ struct G2Runner {
   virtual ~G2Runner() {}
   // out_host: the affine sum, 4 Fq (all zero = infinity)
   virtual void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) = 0;
+  // geometry of the last run, as MsmRunner::shape reports it (out[3] = 0: the pipeline is table-free)
+  virtual void shape(uint32_t out[4]) const = 0;
 };
 
 // One twisted Edwards MSM pipeline (abi_te.hip makes it: MsmPlan<TeOf<T>, HipBackend>, blocking, table-free)
@@ -59,6 +61,8 @@ struct TeRunner {
   virtual ~TeRunner() {}
   // n >= 1 pairs; out_host: the affine sum x || y, 2 Fq (the identity is (0, 1))
   virtual void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) = 0;
+  // geometry of the last run, as MsmRunner::shape reports it (out[3] = 0: the pipeline is table-free)
+  virtual void shape(uint32_t out[4]) const = 0;
 };
 
 struct NttRunner {

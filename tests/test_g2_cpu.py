@@ -169,6 +169,37 @@ def test_g2_msm_stepped_adversarial_scalars(key300):
             assert run_msm(b, ks, n, 0, c, T, T2, K0) == want, (name, c, T)
 
 
+def test_g2_msm_stepped_partial_sums_cancel(key300):
+    """The constructions of test_g2_msm_partial_sums_cancel_in_the_joins (tests/test_g2_msm_gpu.py) stepped on the host: 150 times P
+    and 150 times -P under one scalar, in halves and alternating, sum to the identity (all-zero bytes) under every setting; with one
+    -P turned into P the sum is 2k P.  (The stepped sort keeps index order inside a bucket: here `halves` makes non-trivial partial
+    sums cancel in the joins and `alternating` with the even chunk length 4 makes every lane's own sum the identity.)  This pins the
+    expected values and the plan's logic without a device: a failure of the device test then points at the HIP build."""
+    n = 300
+    P = key300[7]
+    s = (0x9e3779b97f4a7c15 ** 4 + 21) % G.R
+    pn = [P, G.neg(P)]
+    layouts = {"halves": [i >= n // 2 for i in range(n)], "alternating": [bool(i & 1) for i in range(n)]}
+    for name, minus in layouts.items():
+        b = [pn[m] for m in minus]
+        b2 = list(b)
+        b2[[i for i in range(n) if minus[i]][n // 4]] = P
+        for (c, T, T2, K0) in SETTINGS:
+            assert run_msm(b, [s] * n, n, 0, c, T, T2, K0) is G.INF, (name, c, T)
+            assert run_msm(b2, [s] * n, n, 0, c, T, T2, K0) == G.mul(2 * s, P), (name, c, T)
+
+
+def test_g2_msm_stepped_one_base_one_scalar(key300):
+    """test_g2_msm_equal_partial_sums_meet_in_the_joins stepped on the host: every partial sum of a bucket is the same point, the
+    joins take the doubling branch of XyzzD::add over Fq2"""
+    n = 300
+    P = key300[2]
+    for s in ((0x9e3779b97f4a7c15 ** 4 + 5) % G.R, 1, 3):
+        want = G.mul(n * s % G.R, P)
+        for (c, T, T2, K0) in SETTINGS:
+            assert run_msm([P] * n, [s] * n, n, 0, c, T, T2, K0) == want, (s, c, T)
+
+
 def test_g2_small_round_products(key300):
     """The per-lane scalar multiplication of the small-round kernel (g2.hpp ScalarMulBody), summed on the host."""
     for n in (1, 2, 17):

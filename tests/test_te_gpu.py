@@ -215,7 +215,8 @@ def test_te_msm_chains_of_cut_buckets(ctx, pool, n):
 
 @pytest.mark.parametrize("c,T", [(4, 1), (7, 3), (10, 16), (13, 64), (16, 0)])
 def test_te_msm_tunings(ctx, pool, c, T):
-    """window widths and chunk lengths as test_msm_tunings sets them"""
+    """window widths and chunk lengths as test_msm_tunings sets them; the width is read back from the call's shape, so a tuning that
+    was silently ignored fails here"""
     n = 5000
     bases = np.ascontiguousarray(np.tile(E.points_array(pool), (5, 1))[:n])
     ks = rand_scalars(1234, n)
@@ -225,6 +226,7 @@ def test_te_msm_tunings(ctx, pool, c, T):
         k = ctx.upload_te_srs(CURVE, bases)
         try:
             out, _ = k.msm(E.scalars_array(ks, False))
+            assert ctx.last_msm_shape()["window_bits"] == c
             assert E.point_from_bytes(out.tobytes()) == want
         finally:
             k.free()
