@@ -749,10 +749,12 @@ int pc_hip_group_ntt_batch(pc_group* g, pc_curve field_of, const void* in_host, 
  * On the device a key holds x || y || 2dxy per point (96 bytes, the third coordinate made once at upload: the bucket addition is 7
  * multiplications with it and 9 without); upload, read-back and every result are x || y.  A pc_te_srs belongs to its context: counted by
  * pc_hip_ctx_bytes_resident (out[0] and out[5]) and released by pc_hip_shutdown if the caller has not freed it (the handle then only
- * remains to be freed).  The MSM is table-free: no window table, no GLV (the curve has no endomorphism), no captured launch graphs, no
- * host-parts split, no many-MSM form.  The scalar field has 2-adicity 1, so there is no NTT over it; the vector kernels of the halving
- * rounds exist for it (pc_hip_te_fr_powers, pc_hip_te_ipa_fold_dots, pc_hip_te_ipa_key_scalars), and an opening runs on the device in
- * one call, pc_hip_te_ipa_open_rounds, against a committer key that stays resident and unmodified. */
+ * remains to be freed).  The single MSM is table-free: no window table, no GLV (the curve has no endomorphism), no captured launch
+ * graphs, no host-parts split.  The many-MSM form, pc_hip_te_msm_many, runs against a window table of its own (HyraxPC::commit on this
+ * curve, the reference's Hyrax381: hyrax/tests.rs:6,20-21).  The scalar field has 2-adicity 1, so there is no NTT over it; the vector
+ * kernels of the halving rounds exist for it (pc_hip_te_fr_powers, pc_hip_te_ipa_fold_dots, pc_hip_te_ipa_key_scalars) and those of
+ * Hyrax's opening (pc_hip_te_fr_lincomb, pc_hip_te_fr_dot), and an IPA opening runs on the device in one call,
+ * pc_hip_te_ipa_open_rounds, against a committer key that stays resident and unmodified. */
 typedef enum { PC_TE_ED_ON_BLS12_381 = 0 } pc_te_curve;
 typedef struct pc_te_srs pc_te_srs;
 /* The residency hook of InnerProductArgPC::trim (ipa_pc/mod.rs:359-401: comm_key copied at :384): n points x || y, stride_bytes
@@ -763,13 +765,28 @@ void pc_hip_te_srs_free(pc_te_srs* srs);
 size_t pc_hip_te_srs_len(const pc_te_srs* srs);
 /* Points [offset, offset + count) of the key as x || y on the host: final_comm_key of an opening (ipa_pc/mod.rs:718). */
 int pc_hip_te_srs_read(pc_ctx* ctx, const pc_te_srs* srs, size_t offset, size_t count, void* out_host);
-/* {bases (96 bytes a point), 0, fold table, pipeline workspace} -- the layout of pc_hip_srs_bytes_resident; there are no window tables. */
+/* {bases (96 bytes a point), window table of the many-MSM pass (pc_hip_te_msm_many; 0 before its first call), fold table, pipeline
+ * workspaces} -- the layout of pc_hip_srs_bytes_resident. */
 int pc_hip_te_srs_bytes_resident(const pc_te_srs* srs, size_t out[4]);
 /* <G::Group as VariableBaseMSM>::msm_bigint(&comm_key[base_offset..], scalars).into_affine(): cm_commit, ipa_pc/mod.rs:54-72, and with
  * it the L and R of every round (:671-675), blocking.  min(n, len - base_offset) pairs, as msm_bigint truncates.  out_xy: x || y; the
  * identity is written as (0, ONE) -- arkworks' Affine::zero() in Montgomery form -- with *out_is_identity = 1 (optional). */
 int pc_hip_te_msm(pc_ctx* ctx, const pc_te_srs* srs, size_t base_offset, const void* scalars, pc_scalar_form form, pc_mem where,
                   size_t n, void* out_xy, int* out_is_identity);
+/* Many short MSMs over the SAME points in one pass, the contract of pc_hip_msm_many on this curve:
+ *   out[k] = sum_{j < m} scalars[k][j] * key[base_offset + j],   k < n_msms,   scalars = n_msms x m elements, contiguous.
+ * HyraxPC::commit's one Pedersen commitment per matrix row (hyrax/mod.rs:233-242, pedersen_commit :86-93) with key = com_key || h and
+ * scalars[k] = row_k || r_k.  The m points get a window table T[w][j] = 2^(c w) * key[base_offset + j], 96 bytes a record, built on the
+ * device on the first call and cached on the key per (base_offset, m, n_msms) with the pass's pipeline; MSM k owns bucket set k of one
+ * sort / accumulate / reduce pipeline, results are folded per MSM on the device and normalised with one inversion.  The cache is
+ * dropped when another shape is asked for, by pc_hip_te_ec_fold on this key (which changes the points the table was made from), by
+ * pc_hip_te_srs_free and by pc_hip_shutdown; the table is out[1] of pc_hip_te_srs_bytes_resident (and part of out[2] of
+ * pc_hip_ctx_bytes_resident), the pipeline part of out[3].  out_xy: n_msms points x || y; a sum without a non-zero term (an all-zero
+ * row, m == 0) and one that cancels are the identity (0, ONE), flag 1; out_is_identity: n_msms flags or NULL.  Scalar forms and sides
+ * as for pc_hip_te_msm.  A range beyond the key, a null input, a key of another context: PC_ERR_INVALID_ARG; n_msms * m * windows or
+ * n_msms * 2^(c-1) >= 2^31: PC_ERR_TOO_LARGE before anything is allocated; n_msms == 0: PC_OK, nothing written. */
+int pc_hip_te_msm_many(pc_ctx* ctx, pc_te_srs* srs, size_t base_offset, const void* scalars, pc_scalar_form form, pc_mem where,
+                       size_t m, size_t n_msms, void* out_xy, int* out_is_identity);
 /* key[i] = affine(key[i] + u * key[n_half + i]), i < n_half, in place, as pc_hip_ec_fold: `k_l += k_r * u` and normalize_batch,
  * ipa_pc/mod.rs:699-707.  u_host: one Fr, Montgomery.  The key keeps its length; the round's MSMs read its first n_half points. */
 int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* srs, size_t n_half, const void* u_host);
@@ -799,6 +816,12 @@ int pc_hip_te_ipa_fold_dots(pc_ctx* ctx, pc_te_curve curve, void* coeffs_dev, vo
                             void* out_dots_host);
 int pc_hip_te_ipa_key_scalars(pc_ctx* ctx, pc_te_curve curve, const void* coeffs_dev, size_t m, void* s_dev, size_t n0,
                               const void* fold_u_host, size_t fold_m, void* out_l_dev, void* out_r_dev);
+/* The vector kernels of HyraxPC::open over the curve's scalar field: t.row_mul(l) (hyrax/mod.rs:347, and lt at :391) is one
+ * pc_hip_te_fr_lincomb over the rows, <lt, r> (:356) one pc_hip_te_fr_dot.  Contracts, argument checks and error codes of
+ * pc_hip_fr_lincomb and pc_hip_fr_dot, with a pc_te_curve where those take the pc_curve of the field. */
+int pc_hip_te_fr_lincomb(pc_ctx* ctx, pc_te_curve curve, const void* const* polys, pc_mem where_in, const size_t* lens,
+                         size_t k, const void* xi_host, void* out, pc_mem where_out, size_t n_out);
+int pc_hip_te_fr_dot(pc_ctx* ctx, pc_te_curve curve, const void* a_dev, const void* b_dev, size_t n, void* out_host);
 /* The halving rounds of InnerProductArgPC::open (ipa_pc/mod.rs:664-711) in one call, as pc_hip_ipa_open_rounds: arguments and outputs
  * are that call's, with 64-byte points x || y (the identity is (0, ONE)).  Plain launches, no captured graphs; the two MSMs of a round
  * run one after the other on the key's pipeline.  The committer key is never modified: the first fold is out of place (from the fold

@@ -161,6 +161,9 @@ def load_library():
     lib.pc_hip_te_srs_read.argtypes = [vp, vp, sz, sz, vp]
     lib.pc_hip_te_srs_bytes_resident.argtypes = [vp, C.POINTER(sz)]
     lib.pc_hip_te_msm.argtypes = [vp, vp, sz, vp, ip, ip, sz, vp, C.POINTER(ip)]
+    lib.pc_hip_te_msm_many.argtypes = [vp, vp, sz, vp, ip, ip, sz, sz, vp, C.POINTER(ip)]
+    lib.pc_hip_te_fr_lincomb.argtypes = [vp, ip, C.POINTER(vp), ip, C.POINTER(sz), sz, vp, vp, ip, sz]
+    lib.pc_hip_te_fr_dot.argtypes = [vp, ip, vp, vp, sz, vp]
     lib.pc_hip_te_ec_fold.argtypes = [vp, vp, sz, vp]
     lib.pc_hip_te_ec_fold_from.argtypes = [vp, vp, sz, vp, C.POINTER(vp)]
     lib.pc_hip_te_srs_precompute_fold.argtypes = [vp, vp]
@@ -604,6 +607,33 @@ class Context:
         """out_dev[i] = z^i, i < n, over the scalar field of a twisted Edwards curve (pc_hip_te_fr_powers); z_mont: 32 bytes, host."""
         z = np.ascontiguousarray(z_mont)
         self.check(self.lib.pc_hip_te_fr_powers(self.h, TE_CURVES[curve], C.c_void_p(z.ctypes.data), n, _ptr(out_dev)[0]))
+
+    def te_fr_dot(self, curve, a_dev, b_dev, n):
+        """<a, b> over the scalar field of a twisted Edwards curve (pc_hip_te_fr_dot): two device vectors of n Montgomery Fr -> 32 bytes."""
+        out = np.zeros(32, dtype=np.uint8)
+        self.check(self.lib.pc_hip_te_fr_dot(self.h, TE_CURVES[curve], _ptr(a_dev)[0], _ptr(b_dev)[0], n, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def te_fr_lincomb(self, curve, polys, xi, n_out=None, out=None, lens=None):
+        """sum_j xi[j] * polys[j] over the scalar field of a twisted Edwards curve (pc_hip_te_fr_lincomb; Hyrax's row_mul).
+        polys: list of (len_j, 32) uint8 host arrays, or device pointers with `lens`; xi: (k, 32) uint8 Montgomery Fr on the host.
+        Returns `out` (a device pointer / tensor if given, else a new (n_out, 32) uint8 host array)."""
+        k = len(polys)
+        ptrs = [_ptr(p) for p in polys]
+        where = ptrs[0][1] if k else PC_MEM_HOST
+        assert all(w == where for _, w in ptrs)
+        if lens is None:
+            lens = [p.shape[0] for p in polys]
+        if n_out is None:
+            n_out = max(lens) if k else 0
+        if out is None:
+            out = np.zeros((n_out, 32), dtype=np.uint8)
+        pout, wout = _ptr(out)
+        arr = (C.c_void_p * max(k, 1))(*[p for p, _ in ptrs])
+        larr = (C.c_size_t * max(k, 1))(*lens)
+        xi = np.ascontiguousarray(xi)
+        self.check(self.lib.pc_hip_te_fr_lincomb(self.h, TE_CURVES[curve], arr, where, larr, k, C.c_void_p(xi.ctypes.data), pout, wout, n_out))
+        return out
 
     def te_ipa_fold_dots(self, curve, coeffs_dev, z_dev, m, u=None, u_inv=None):
         """pc_hip_te_ipa_fold_dots: optional fold at size 2m by (u, u^-1), then the round's two inner products at size m -> (2, 32) uint8."""
@@ -1160,6 +1190,20 @@ class TeSrs:
                                                   PC_SCALARS_MONTGOMERY if montgomery else PC_SCALARS_CANONICAL,
                                                   where, n, C.c_void_p(out.ctypes.data), C.byref(ident)))
         return out, bool(ident.value)
+
+    def msm_many(self, scalars, m=None, n_msms=None, base_offset=0, montgomery=False):
+        """n_msms MSMs of m pairs over bases[base_offset : base_offset + m] in one pass (pc_hip_te_msm_many; Hyrax's one commitment per
+        matrix row).  scalars: (n_msms, m, 32) uint8 host array, or a device pointer / tensor with m and n_msms.
+        Returns ((n_msms, 64) uint8 points x || y, (n_msms,) identity flags)."""
+        p, where = _ptr(scalars)
+        if m is None:
+            n_msms, m = scalars.shape[0], scalars.shape[1]
+        out = np.zeros((n_msms, TE_POINT_BYTES[self.curve]), dtype=np.uint8)
+        ident = (C.c_int * max(n_msms, 1))()
+        self.ctx.check(self.ctx.lib.pc_hip_te_msm_many(self.ctx.h, self.h, base_offset, p,
+                                                       PC_SCALARS_MONTGOMERY if montgomery else PC_SCALARS_CANONICAL, where, m, n_msms,
+                                                       C.c_void_p(out.ctypes.data), ident))
+        return out, np.array(list(ident)[:n_msms], dtype=bool)
 
     def ec_fold(self, n_half, u_mont):
         """key[i] = key[i] + u * key[n_half + i], i < n_half, in place (pc_hip_te_ec_fold); u_mont: one Montgomery Fr (host, 32 bytes)."""

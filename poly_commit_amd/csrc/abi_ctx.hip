@@ -87,7 +87,7 @@ int pc_hip_ctx_bytes_resident(pc_ctx* ctx, size_t out[6]) {
   for (int i = 0; i < 6; i++) out[i] = 0;
   out[0] = pc::dev_bytes_held(ctx->device);
   out[5] = keys_bytes(ctx, out + 1) + ctx->g2_keys.size() + ctx->te_keys.size();      // (G2 and twisted Edwards keys: counted here and, through the ledger, in out[0])
-  for (const pc_te_srs* k : ctx->te_keys) out[3] += te_fold_table_bytes(k);            // their fold tables (pc_hip_te_srs_precompute_fold)
+  for (const pc_te_srs* k : ctx->te_keys) { out[2] += k->many.table_bytes; out[3] += te_fold_table_bytes(k); }      // their window tables (pc_hip_te_msm_many) and fold tables (pc_hip_te_srs_precompute_fold)
   out[4] = ctx->be.scratch_bytes();
   return PC_OK;
 }

@@ -1,5 +1,6 @@
 // C ABI of the gfx950 backend (include/pc_hip.h): the twisted Edwards curve ed_on_bls12_381 (JubJub) -- typed keys, the MSM and the key
-// fold of InnerProductArgPC over it (ipa_pc/mod.rs:54-72, 699-707).  This unit also instantiates everything templated on TeOf<T>
+// fold of InnerProductArgPC over it (ipa_pc/mod.rs:54-72, 699-707), and the many-MSM pass of HyraxPC::commit over a window table of a
+// key range (hyrax/mod.rs:233-242).  This unit also instantiates everything templated on TeOf<T>
 // (te.hpp, MsmPlan<TeOf<T>, HipBackend> with the digit and sort stages of its scalar field), and nothing of a short Weierstrass group.
 #include <vector>
 #include "abi.hpp"
@@ -15,11 +16,12 @@ constexpr int TE_AW = AffD<TeC>::WORDS, TE_XY = AffD<TeC>::XY_WORDS, TE_XW = Xyz
 constexpr size_t TE_POINT_BYTES = (size_t)TE_XY * 4;      // the caller's x || y
 constexpr uint32_t TE_NORM_K = 16;                        // points per inversion of the fold's normalisation (JacBatchAffineBody's default)
 
-// One blocking, table-free MSM pipeline: plain launches (no captured graphs), host scalars staged whole (no parts)
+// One blocking MSM pipeline: plain launches (no captured graphs), host scalars staged whole (no parts).  subs == 0: the table-free
+// single MSM; subs == B: the many-MSM pass against cfg's window table (`run` then takes B x m scalars and writes B points)
 struct TeRunnerT : TeRunner {
   HipBackend& be;
   MsmPlan<TeC, HipBackend> plan;
-  TeRunnerT(HipBackend& b, size_t n_max, const MsmConfig& cfg) : be(b), plan(b, n_max, cfg) {}
+  TeRunnerT(HipBackend& b, size_t n_max, const MsmConfig& cfg, uint32_t subs = 0) : be(b), plan(b, n_max, cfg, subs) {}
   void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) override {
     const uint32_t* sdev = (const uint32_t*)scalars;
     be.n_ev = 0; be.mark();
@@ -28,9 +30,17 @@ struct TeRunnerT : TeRunner {
   }
   void shape(uint32_t out[4]) const override {
     const MsmGeom& g = plan.last_geom();
-    out[0] = g.c; out[1] = g.Wd; out[2] = g.NB; out[3] = 0;
+    out[0] = g.c; out[1] = g.Wd; out[2] = g.NB; out[3] = g.tbl_stride ? 1u : 0u;
   }
 };
+
+// The window table of the m resident points at b0 (te.hpp) on the context's queue, the doubled rows staged in its workspace.  Returns
+// with the queue drained.
+void te_window_table_sync(HipBackend& be, const uint32_t* b0, size_t m, uint32_t c, uint32_t Wd, uint32_t* table) {
+  uint32_t* ext = (uint32_t*)be.workspace(m * (size_t)(TE_XW + TE_FQ_W) * 4);
+  te_window_table<TeC>(be, b0, m, c, Wd, table, ext, ext + m * (size_t)TE_XW, TE_NORM_K);
+  be.sync();
+}
 
 TeLane* te_lane(pc_te_srs* k) {
   if (k->lane) return k->lane;
@@ -149,6 +159,52 @@ int pc_hip_te_msm(pc_ctx* ctx, const pc_te_srs* kc, size_t base_offset, const vo
   });
 }
 
+int pc_hip_te_msm_many(pc_ctx* ctx, pc_te_srs* k, size_t base_offset, const void* scalars, pc_scalar_form form, pc_mem where,
+                       size_t m, size_t n_msms, void* out_xy, int* out_is_identity) {
+  if (!ctx || !k || k->ctx != ctx || !out_xy || (m && n_msms && !scalars)) return PC_ERR_INVALID_ARG;
+  if (base_offset > k->n || m > k->n - base_offset) return PC_ERR_INVALID_ARG;
+  if (where != PC_MEM_HOST && where != PC_MEM_DEVICE) return PC_ERR_INVALID_ARG;
+  if (form != PC_SCALARS_CANONICAL && form != PC_SCALARS_MONTGOMERY) return PC_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    if (!n_msms) return (int)PC_OK;
+    uint32_t* out = (uint32_t*)out_xy;
+    if (!m) {                                      // empty sums: identities, no device work
+      for (size_t i = 0; i < n_msms; i++) { pc::write_identity(out + i * (size_t)TE_XY); if (out_is_identity) out_is_identity[i] = 1; }
+      return (int)PC_OK;
+    }
+    const uint32_t c = pc::msm_choose_table_c(m, pc::TeFrP::BITS, 0), Wd = pc::msm_num_windows(pc::TeFrP::BITS, c);
+    if ((uint64_t)n_msms * m * Wd >= (1ull << 31) || ((uint64_t)n_msms << (c - 1)) >= (1ull << 31)) return (int)PC_ERR_TOO_LARGE;
+    pc_te_srs::Many& M = k->many;
+    if (!M.lane || M.base_offset != base_offset || M.m != m || M.B != n_msms) {
+      te_drop_many(k);
+      const size_t bytes = (size_t)Wd * m * (size_t)TE_AW * 4;
+      uint32_t* table = (uint32_t*)ctx->be.alloc(bytes);
+      TeLane* L = nullptr;
+      try {
+        pc::te_window_table_sync(ctx->be, k->bases + base_offset * (size_t)TE_AW, m, c, Wd, table);
+        L = new TeLane();
+        L->be.init();
+        pc::MsmConfig cfg = ctx->msm_cfg;
+        cfg.c = 0; cfg.T = 0; cfg.tbl = table; cfg.tbl_c = c; cfg.tbl_stride = (uint32_t)m; cfg.tbl_pt_stride = (uint32_t)TE_AW; cfg.tbl_min_n = 0;
+        cfg.tbl_glv = false;
+        cfg.coop2_max_points = 0;      // one lane per point in every cooperative level, as for the single MSM
+        L->runner = new pc::TeRunnerT(L->be, n_msms * m, cfg, (uint32_t)n_msms);
+      } catch (...) { (void)hipStreamSynchronize(ctx->be.stream); delete L; ctx->be.free(table); throw; }
+      M.table = table; M.table_bytes = bytes; M.lane = L; M.base_offset = base_offset; M.m = m; M.B = n_msms;
+    }
+    TeLane* L = M.lane;
+    L->be.timing = ctx->be.timing;
+    L->runner->run(k->bases, 0, scalars, where, n_msms * m, form == PC_SCALARS_MONTGOMERY, out);
+    L->runner->shape(ctx->shape);
+    if (out_is_identity)
+      for (size_t i = 0; i < n_msms; i++) out_is_identity[i] = pc::host64::te_is_identity<pc_te_ed_on_bls12_381>(out + i * (size_t)TE_XY) ? 1 : 0;
+    for (int i = 0; i < 8; i++) ctx->phases[i] = 0;
+    if (L->be.timing) for (int i = 0; i + 1 < L->be.n_ev && i < 8; i++) (void)hipEventElapsedTime(&ctx->phases[i], L->be.ev[i], L->be.ev[i + 1]);
+    return (int)PC_OK;
+  });
+}
+
 int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* k, size_t n_half, const void* u_host) {
   if (!ctx || !k || k->ctx != ctx || !u_host || 2 * n_half > k->n) return PC_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
@@ -156,6 +212,7 @@ int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* k, size_t n_half, const void* u_ho
     if (!n_half) return (int)PC_OK;
     pc::HipBackend& be = ctx->be;
     te_drop_fold_table(k);       // the key changes: its fold table is stale, and what was known about its points
+    te_drop_many(k);             // ... and the window table of its many-MSM pass
     k->in_subgroup = -1;
     // the sums in extended coordinates, then the prefix products of the normalisation
     uint32_t* ext = (uint32_t*)be.workspace(n_half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);

@@ -1,6 +1,7 @@
 // C ABI of the gfx950 backend (include/pc_hip.h): InnerProductArgPC::open over ed_on_bls12_381 (JubJub) on the device -- the vector
 // kernels of the halving rounds over the curve's 252-bit scalar field, and the rounds as one call (ipa_pc/mod.rs:664-711).
-// This unit instantiates the members of FieldOpsImpl that the rounds need for that field and no other: its 2-adicity is 1, there is
+// With them the two vector kernels of HyraxPC::open over that field, fr_lincomb and fr_dot (hyrax/mod.rs:347,356,391).
+// This unit instantiates the members of FieldOpsImpl that the rounds and Hyrax need for that field and no other: its 2-adicity is 1, there is
 // no NTT over it (and nothing of a FieldOps table: pc_curve keeps its four ids).  The group side is abi_te.hip's, through the C ABI.
 #include <chrono>
 #include <string.h>
@@ -26,6 +27,55 @@ int pc_hip_te_fr_powers(pc_ctx* ctx, pc_te_curve curve, const void* z_host, size
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
     if (n) TeFr::fr_powers(ctx->be, (const uint32_t*)z_host, n, (uint32_t*)out_dev);
+    return (int)PC_OK;
+  });
+}
+
+// <a, b> and sum_j xi[j] * polys[j] over the curve's scalar field: HyraxPC::open's <lt, r> and t.row_mul(l) (hyrax/mod.rs:347,356,391)
+int pc_hip_te_fr_dot(pc_ctx* ctx, pc_te_curve curve, const void* a_dev, const void* b_dev, size_t n, void* out_host) {
+  if (!ctx || !out_host || (n && (!a_dev || !b_dev))) return PC_ERR_INVALID_ARG;
+  if (int rc = te_curve_check(curve)) return rc;
+  if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    TeFr::fr_dot(ctx->be, (const uint32_t*)a_dev, (const uint32_t*)b_dev, n, (uint32_t*)out_host);
+    return (int)PC_OK;
+  });
+}
+
+int pc_hip_te_fr_lincomb(pc_ctx* ctx, pc_te_curve curve, const void* const* polys, pc_mem where_in, const size_t* lens,
+                         size_t k, const void* xi_host, void* out, pc_mem where_out, size_t n_out) {
+  if (!ctx || (k && (!polys || !lens || !xi_host)) || (n_out && !out)) return PC_ERR_INVALID_ARG;
+  if (int rc = te_curve_check(curve)) return rc;
+  if (n_out >= (1ull << 32) || k >= (1ull << 20)) return PC_ERR_TOO_LARGE;
+  size_t total = 0;
+  for (size_t j = 0; j < k; j++) {
+    if (lens[j] >= (1ull << 32)) return PC_ERR_TOO_LARGE;
+    if (lens[j] && !polys[j]) return PC_ERR_INVALID_ARG;
+    total += lens[j];
+  }
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  return guarded(ctx, [&]() {
+    if (!n_out) return (int)PC_OK;
+    // host vectors are staged back to back in one device buffer; the three small argument arrays side by side in the context's scratch
+    Staged stage(ctx->be, nullptr, PC_MEM_HOST, where_in == PC_MEM_HOST ? total * TE_FR_BYTES : 0, false, 0);
+    std::vector<uint64_t> addr(k ? k : 1, 0); std::vector<uint32_t> len32(k ? k : 1, 0);
+    size_t off = 0;
+    for (size_t j = 0; j < k; j++) {
+      len32[j] = (uint32_t)lens[j];
+      if (where_in == PC_MEM_HOST) {
+        if (lens[j]) ctx->be.copy_h2d((char*)stage.dev + off * TE_FR_BYTES, polys[j], lens[j] * TE_FR_BYTES);
+        addr[j] = (uint64_t)(uintptr_t)((char*)stage.dev + off * TE_FR_BYTES); off += lens[j];
+      } else addr[j] = (uint64_t)(uintptr_t)polys[j];
+    }
+    const size_t kk = k ? k : 1, o_len = kk * 8, o_xi = (o_len + kk * 4 + 31) & ~(size_t)31;
+    char* args = (char*)ctx->be.workspace(o_xi + kk * TE_FR_BYTES);
+    ctx->be.copy_h2d(args, addr.data(), kk * 8);
+    ctx->be.copy_h2d(args + o_len, len32.data(), kk * 4);
+    if (k) ctx->be.copy_h2d(args + o_xi, xi_host, k * TE_FR_BYTES);
+    Staged sout(ctx->be, out, where_out, n_out * TE_FR_BYTES, false, 1);
+    TeFr::fr_lincomb(ctx->be, args, args + o_len, args + o_xi, k, sout.dev, n_out);
+    if (where_out == PC_MEM_HOST) ctx->be.copy_d2h(out, sout.dev, n_out * TE_FR_BYTES); else ctx->be.sync();
     return (int)PC_OK;
   });
 }

@@ -37,12 +37,14 @@ template <class C1> struct ScalarCurveOf<G2Of<C1>> { typedef C1 type; static con
 template <class T> struct TeOf { typedef T Curve; typedef typename T::FqP FqP; typedef typename T::FrP FrP; };
 template <class T> struct CoordOf<TeOf<T>> { typedef Fd<typename T::FqP> type; };
 template <class T> struct ScalarCurveOf<TeOf<T>> { typedef TeOf<T> type; static constexpr bool IS_G2 = false; };
-// What the MSM templates ask of a group beyond its point types.  TABLE_FREE: no window table, no GLV split, no many-MSM mode
-// (MsmPlan refuses them).  TWO_LANE: HalfAdd below, the XYZZ addition spread over a lane pair, exists for it.
+// What the MSM templates ask of a group beyond its point types.  TABLE_FREE: no window table for the single MSM, no GLV split
+// (MsmPlan refuses them).  MANY_MSM: the many-MSM mode, which runs against a window table of its own, exists for it (G1, and a
+// twisted Edwards group with the table of te.hpp's TeWindowRowBody; not G2).  TWO_LANE: HalfAdd below, the XYZZ addition spread over
+// a lane pair, exists for it.
 template <class C> struct GroupKind {
-  static constexpr bool IS_TE = false, TABLE_FREE = ScalarCurveOf<C>::IS_G2, TWO_LANE = !ScalarCurveOf<C>::IS_G2;
+  static constexpr bool IS_TE = false, TABLE_FREE = ScalarCurveOf<C>::IS_G2, MANY_MSM = !ScalarCurveOf<C>::IS_G2, TWO_LANE = !ScalarCurveOf<C>::IS_G2;
 };
-template <class T> struct GroupKind<TeOf<T>> { static constexpr bool IS_TE = true, TABLE_FREE = true, TWO_LANE = false; };
+template <class T> struct GroupKind<TeOf<T>> { static constexpr bool IS_TE = true, TABLE_FREE = true, MANY_MSM = true, TWO_LANE = false; };
 
 template <class C>
 struct AffD {

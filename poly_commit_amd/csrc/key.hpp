@@ -536,7 +536,16 @@ struct pc_te_srs : pc_key_base {
   uint32_t* fold_tbl = nullptr;  // fold table (pc_hip_te_srs_precompute_fold): fold_rows rows of the n / 2 upper points and their doublings, or null
   uint32_t fold_rows = 0;
   int in_subgroup = -1;          // pc_hip_te_srs_in_subgroup's cached answer (-1: not asked yet)
+  // many-MSM pass (pc_hip_te_msm_many), cached per shape as pc_srs::Many is: the window table of bases[base_offset .. base_offset + m)
+  // (Wd rows of m resident records, from the context's allocator) and a pipeline of its own with B bucket sets
+  struct Many { size_t base_offset = 0, m = 0, B = 0; uint32_t* table = nullptr; size_t table_bytes = 0; TeLane* lane = nullptr; } many;
 };
+// the table and pipeline of the many-MSM pass go back: another shape is asked for, the key's points change (pc_hip_te_ec_fold), the key is released
+inline void te_drop_many(pc_te_srs* k) {
+  delete k->many.lane;
+  if (k->many.table) k->ctx->be.free(k->many.table);
+  k->many = pc_te_srs::Many();
+}
 inline void te_drop_fold_table(pc_te_srs* k) {
   if (k->fold_tbl) k->ctx->be.free(k->fold_tbl);
   k->fold_tbl = nullptr; k->fold_rows = 0;
@@ -547,6 +556,7 @@ inline void te_key_release_device(pc_te_srs* k) {
   (void)hipSetDevice(k->ctx->device);
   delete k->lane; k->lane = nullptr;
   te_drop_fold_table(k);
+  te_drop_many(k);
   key_base_release(k->ctx->te_keys, k);
 }
 inline void te_key_free(pc_te_srs* k) { te_key_release_device(k); delete k; }
@@ -556,12 +566,15 @@ inline pc_te_srs* te_key_create(pc_ctx* ctx, pc_te_curve curve, size_t n, size_t
   if (k) k->te_curve = curve;
   return k;
 }
-// {bases, 0, fold table, pipeline} bytes of one key (the layout of key_bytes: no window tables)
+// {bases, window table of the many-MSM pass, fold table, pipelines} bytes of one key (the layout of key_bytes)
 inline void te_key_bytes(const pc_te_srs* k, size_t out[4]) {
-  out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = 0; out[2] = te_fold_table_bytes(k);
-  out[3] = k->lane ? k->lane->be.bytes_live : 0;
+  out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = k->many.table_bytes; out[2] = te_fold_table_bytes(k);
+  out[3] = (k->lane ? k->lane->be.bytes_live : 0) + (k->many.lane ? k->many.lane->be.bytes_live : 0);
 }
 inline void te_keys_shutdown(pc_ctx* ctx) { key_registry_shutdown(ctx->te_keys, te_key_release_device); }
 inline void te_keys_trim(pc_ctx* ctx) {
-  for (pc_te_srs* k : ctx->te_keys) if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }
+  for (pc_te_srs* k : ctx->te_keys) {
+    if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }
+    if (k->many.lane) { k->many.lane->be.sync(); k->many.lane->be.trim(); }
+  }
 }

@@ -888,7 +888,8 @@ class MsmPlan {
   // n_max / B pairs over the same bases (cfg.tbl must hold their window table); see enqueue().
   MsmPlan(Backend& be, size_t n_max, const MsmConfig& cfg, uint32_t subs = 0) : be_(be), cfg_(cfg), n_max_(n_max), subs_(subs) {
     if (subs_ && (!cfg_.tbl || !cfg_.tbl_c || n_max % subs_)) throw std::runtime_error("MsmPlan: many-MSM mode needs a window table");
-    if (G2 && (subs_ || cfg_.tbl)) throw std::runtime_error("MsmPlan: G2 and twisted Edwards groups are table-free");
+    // (a twisted Edwards group has the many-MSM mode and its table, te.hpp; its single MSM stays table-free, as all of G2 does)
+    if (G2 && (subs_ ? !GroupKind<C>::MANY_MSM : cfg_.tbl != nullptr)) throw std::runtime_error("MsmPlan: G2 and twisted Edwards groups are table-free");
     if (cfg_.T2 < 4) cfg_.T2 = 4;       // each level must shrink the list: 2*ceil(s/T2) < s
     if (cfg_.T2b < 4) cfg_.T2b = 4;
     // plan_geometry divides the bucket count by these and turns them into Horner exponents: powers of two only
@@ -1167,6 +1168,15 @@ class MsmPlan {
   // Wait for the queued MSM and fold its partial sums on the host (Horner) into one affine point.
   void finish(uint32_t* out_host) {
     if (subs_) {      // subs_ affine points: batch-normalise the folded XYZZ results (one inversion in all)
+      if constexpr (GroupKind<C>::IS_TE) {
+        // results are x || y, and a sub-MSM without a non-zero digit (an all-zero row, an empty call) is the identity (0, ONE), never
+        // zeros: its folded sum is the empty word pattern, which batch_to_affine writes as the identity; a sum that passes through or
+        // ends at the true identity is an ordinary value with Z != 0
+        if (pending_empty_) { std::vector<uint32_t> empty((size_t)subs_ * Pt::WORDS, 0u); host64::batch_to_affine<C>(empty.data(), subs_, out_host); return; }
+        be_.wait_done();
+        host64::batch_to_affine<C>(result_host_, subs_, out_host);
+        return;
+      }
       if (pending_empty_) { for (size_t i = 0; i < (size_t)subs_ * AW; i++) out_host[i] = 0; return; }
       be_.wait_done();
       if constexpr (!G2) if (g_.glv) {      // sub-MSM k = set 2k + phi(set 2k + 1)

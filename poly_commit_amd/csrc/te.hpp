@@ -209,6 +209,42 @@ struct TeDblRowBody {
   }
 };
 
+// ---- the window table of a key range (pc_hip_te_msm_many) --------------------------------------------------------------------
+// T[w][j] = 2^(c w) * key[base_offset + j] for w < Wd, row-major in j, every record in the resident form: with it the many-MSM pass
+// puts all windows of a sub-MSM into ONE bucket set (MsmPlan, subs > 0; HyraxPC::commit, hyrax/mod.rs:233-242).  Row w + 1 is row w
+// doubled c times in extended coordinates, then one TeBatchAffineBody over the row -- TeDblRowBody with every c-th row kept.  The
+// doubling is dbl-2008-hwcd under the complete law: points of order 2, 4 and 8 and the identity go through the same instructions; an
+// all-zero record stays empty and is normalised to the identity, which the accumulation adds as it would skip the empty one.
+template <class G>
+struct TeWindowRowBody {
+  typedef XyzzD<G> Pt;
+  typedef AffD<G> Aff;
+  const uint32_t* in; uint32_t* ext; uint32_t c;
+  PC_HD void operator()(uint32_t j) const {
+    const Aff a = Aff::load(in + (size_t)j * Aff::WORDS);
+    uint32_t* o = ext + (size_t)j * Pt::WORDS;
+    if (a.is_inf()) { for (int w = 0; w < Pt::WORDS; w++) o[w] = 0; return; }
+    Pt p; p.X = a.x; p.Y = a.y; p.Z = Pt::Fq::one(); p.Tc = a.x.mul(a.y);
+    for (uint32_t k = 0; k < c; k++) p = p.dbl();
+    p.store(o);
+  }
+};
+
+// The whole table on the backend's queue: row 0 is the range as it is (an all-zero record stays all zero there: the accumulation skips
+// it), row w + 1 is row w through TeWindowRowBody and TeBatchAffineBody with K points per inversion.  ext: m extended points,
+// scratch: m Fq, both the caller's.  Returns with everything queued.
+template <class G, class Backend>
+void te_window_table(Backend& be, const uint32_t* b0, size_t m, uint32_t c, uint32_t Wd, uint32_t* table, uint32_t* ext, uint32_t* scratch, uint32_t K) {
+  const size_t row_words = m * (size_t)AffD<G>::WORDS;
+  be.copy_d2d(table, b0, row_words * 4);
+  for (uint32_t w = 0; w + 1 < Wd; w++) {
+    TeWindowRowBody<G> d{table + w * row_words, ext, c};
+    be.launch(d, m);
+    TeBatchAffineBody<G> nb{ext, scratch, table + (w + 1) * row_words, (uint32_t)m, K};
+    be.launch(nb, (m + K - 1) / K);
+  }
+}
+
 // the non-zero NAF digits of a fold challenge, one entry each: the table row in bits 0..14, bit 15 set for digit -1.  Made once on
 // the host and passed by value: every lane of a wave walks the same list (no divergence, the entries come through the scalar unit).
 struct TeFoldDigits {
