@@ -3,7 +3,7 @@
 // and nothing of G1: the G1 half of the setup goes through pc::curve_ops.
 #include <chrono>
 #include "abi.hpp"
-#include "hip_backend_msm.hpp"
+#include "blocking_lane.hpp"
 #include "fixed_base.hpp"
 
 namespace pc {
@@ -13,36 +13,13 @@ typedef G2Of<pc_curve_bls12_381> G2C;
 typedef pc_curve_bls12_381::FrP FrP;
 constexpr int G2_AW = AffD<G2C>::WORDS, G2_XW = XyzzD<G2C>::WORDS, FR_W = FrP::N;
 
-// One blocking, table-free G2 MSM pipeline: plain launches (no captured graphs), host scalars staged whole (no parts)
-struct G2RunnerT : G2Runner {
-  HipBackend& be;
-  MsmPlan<G2C, HipBackend> plan;
-  G2RunnerT(HipBackend& b, size_t n_max, const MsmConfig& cfg) : be(b), plan(b, n_max, cfg) {}
-  void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) override {
-    const uint32_t* sdev = (const uint32_t*)scalars;
-    be.n_ev = 0; be.mark();
-    if (where == PC_MEM_HOST && n) { be.copy_h2d(plan.scalar_staging(), scalars, n * (size_t)FR_W * 4); sdev = plan.scalar_staging(); }
-    plan.run(bases, base_off, sdev, n, from_mont, out_host);
-  }
-  void shape(uint32_t out[4]) const override {
-    const MsmGeom& g = plan.last_geom();
-    out[0] = g.c; out[1] = g.Wd; out[2] = g.NB; out[3] = 0;
-  }
-};
-
-G2Lane* g2_lane(pc_g2_srs* k) {
+// the key's one pipeline (table-free: the plan refuses a G2 table), created on first use
+BlockingLane* g2_lane(pc_g2_srs* k) {
   if (k->lane) return k->lane;
-  G2Lane* L = new G2Lane();
-  try {
-    L->be.init();
-    MsmConfig cfg = k->ctx->msm_cfg;
-    cfg.tbl = nullptr; cfg.tbl_c = 0;
-    cfg.coop2_max_points = 0;      // one lane per point in every cooperative level (the two-lane form splits Fq coordinates)
-    cfg.K1 = 128;                  // a cooperative level's LDS tile: 128 points x 384 bytes = 48 KiB
-    L->runner = new G2RunnerT(L->be, k->n, cfg);
-  } catch (...) { delete L; throw; }
-  k->lane = L;
-  return L;
+  MsmConfig cfg = k->ctx->msm_cfg;
+  cfg.tbl = nullptr; cfg.tbl_c = 0;
+  cfg.K1 = 128;                  // a cooperative level's LDS tile: 128 points x 384 bytes = 48 KiB
+  return k->lane = blocking_lane<G2C>(k->n, cfg, 0);
 }
 
 // the rounds of an opening with at most this many pairs run as one small kernel (k_small_msm) instead of the full pipeline
@@ -102,18 +79,10 @@ int pc_hip_g2_srs_upload(pc_ctx* ctx, pc_curve curve, const void* bases, size_t 
   if (stride_bytes < pb) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 31)) return PC_ERR_TOO_LARGE;
   if (where == PC_MEM_DEVICE && stride_bytes != pb) return PC_ERR_UNSUPPORTED;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  *out = nullptr;
-  pc_g2_srs* k = nullptr;
-  int rc = guarded(ctx, [&]() {
-    k = g2_key_create(ctx, curve, n);
-    if (!k) return (int)PC_ERR_OOM;
+  return key_make(ctx, out, [&]() { return g2_key_create(ctx, curve, n); }, g2_key_free, [&](pc_g2_srs* k) {
     key_base_fill(k, bases, n, stride_bytes, where);
     return (int)PC_OK;
   });
-  if (rc != PC_OK) { if (k) g2_key_free(k); return rc; }
-  *out = k;
-  return PC_OK;
 }
 
 void pc_hip_g2_srs_free(pc_g2_srs* k) { key_free_locked(k, g2_key_free); }
@@ -264,10 +233,10 @@ int pc_hip_g2_msm(pc_ctx* ctx, const pc_g2_srs* kc, size_t base_offset, const vo
   if (n && !scalars) return PC_ERR_INVALID_ARG;
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
-    G2Lane* L = pc::g2_lane(k);
+    BlockingLane* L = pc::g2_lane(k);
     L->be.timing = ctx->be.timing;
     L->runner->run(k->bases, (uint32_t)base_offset, scalars, where, n, form == PC_SCALARS_MONTGOMERY, (uint32_t*)out_xy);
-    if (n) L->runner->shape(ctx->shape);      // (pc_hip_last_msm_shape; an empty call plans nothing)
+    if (n) lane_phases(ctx, L);      // (pc_hip_last_msm_shape, pc_hip_last_msm_phases_ms; an empty call plans nothing)
     if (out_is_infinity) *out_is_infinity = affine_is_zero((const uint32_t*)out_xy, G2_AW);
     return (int)PC_OK;
   });
@@ -317,7 +286,7 @@ int pc_hip_ml_open(pc_ctx* ctx, const pc_g2_srs* kc, const void* evals, pc_mem w
     uint32_t* q = (uint32_t*)work.dev;
     uint32_t* rbuf[2] = {q + (n / 2) * FR_W, q + (n / 2 + n / 2) * FR_W};
     const uint32_t* r_in = (const uint32_t*)ev.dev;
-    G2Lane* L = pc::g2_lane(k);
+    BlockingLane* L = pc::g2_lane(k);
     L->be.timing = false;
     for (unsigned i = 0; i < nv; i++) {
       const size_t half = n >> (i + 1), off = n - (n >> i);

@@ -1,7 +1,7 @@
 // C ABI of the gfx950 backend (include/pc_hip.h): IPA -- vector kernels, key folds, the opening loop.
 #include <chrono>
 #include <string.h>
-#include "abi.hpp"
+#include "abi_fr.hpp"
 
 extern "C" {
 
@@ -16,48 +16,22 @@ int pc_hip_fr_fold(pc_ctx* ctx, pc_curve field_of, void* lo_dev, const void* hi_
   });
 }
 int pc_hip_fr_dot(pc_ctx* ctx, pc_curve field_of, const void* a_dev, const void* b_dev, size_t n, void* out_host) {
-  if (!ctx || !pc_known_curve(field_of) || !out_host || (n && (!a_dev || !b_dev))) return PC_ERR_INVALID_ARG;
-  if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    pc::field_ops(field_of).fr_dot(ctx->be, (const uint32_t*)a_dev, (const uint32_t*)b_dev, n, (uint32_t*)out_host);
-    return (int)PC_OK;
-  });
+  if (!pc_known_curve(field_of)) return PC_ERR_INVALID_ARG;
+  return fr_dot_call(ctx, pc::field_ops(field_of), a_dev, b_dev, n, out_host);
 }
 int pc_hip_ipa_fold_dots(pc_ctx* ctx, pc_curve field_of, void* coeffs_dev, void* z_dev, size_t m, const void* u_host, const void* u_inv_host,
                          void* out_dots_host) {
-  if (!ctx || !pc_known_curve(field_of) || !coeffs_dev || !z_dev || !out_dots_host || !m || (m & (m - 1))) return PC_ERR_INVALID_ARG;
-  if ((u_host != nullptr) != (u_inv_host != nullptr)) return PC_ERR_INVALID_ARG;
-  if (m >= (1ull << 31)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    pc::field_ops(field_of).ipa_fold_dots(ctx->be, (uint32_t*)coeffs_dev, (uint32_t*)z_dev, m, (const uint32_t*)u_host, (const uint32_t*)u_inv_host,
-                                          (uint32_t*)out_dots_host);
-    return (int)PC_OK;
-  });
+  if (!pc_known_curve(field_of)) return PC_ERR_INVALID_ARG;
+  return ipa_fold_dots_call(ctx, pc::field_ops(field_of), coeffs_dev, z_dev, m, u_host, u_inv_host, out_dots_host);
 }
 int pc_hip_fr_powers(pc_ctx* ctx, pc_curve field_of, const void* z_host, size_t n, void* out_dev) {
-  if (!ctx || !pc_known_curve(field_of) || !z_host || (n && !out_dev)) return PC_ERR_INVALID_ARG;
-  if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    if (n) pc::field_ops(field_of).fr_powers(ctx->be, (const uint32_t*)z_host, n, (uint32_t*)out_dev);
-    return (int)PC_OK;
-  });
+  if (!pc_known_curve(field_of)) return PC_ERR_INVALID_ARG;
+  return fr_powers_call(ctx, pc::field_ops(field_of), z_host, n, out_dev);
 }
 int pc_hip_ipa_key_scalars(pc_ctx* ctx, pc_curve field_of, const void* coeffs_dev, size_t m, void* s_dev, size_t n0,
                            const void* fold_u_host, size_t fold_m, void* out_l_dev, void* out_r_dev) {
-  if (!ctx || !pc_known_curve(field_of) || !s_dev || !n0 || (n0 & (n0 - 1))) return PC_ERR_INVALID_ARG;
-  if (fold_u_host && (fold_m < 2 || (fold_m & (fold_m - 1)) || fold_m > n0)) return PC_ERR_INVALID_ARG;
-  if ((out_l_dev != nullptr) != (out_r_dev != nullptr)) return PC_ERR_INVALID_ARG;
-  if (out_l_dev && (!coeffs_dev || m < 2 || (m & (m - 1)) || m > n0)) return PC_ERR_INVALID_ARG;
-  if (n0 >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    pc::field_ops(field_of).ipa_key_scalars(ctx->be, (const uint32_t*)coeffs_dev, m, (uint32_t*)s_dev, n0, (const uint32_t*)fold_u_host, fold_m,
-                                            (uint32_t*)out_l_dev, (uint32_t*)out_r_dev);
-    return (int)PC_OK;
-  });
+  if (!pc_known_curve(field_of)) return PC_ERR_INVALID_ARG;
+  return ipa_key_scalars_call(ctx, pc::field_ops(field_of), coeffs_dev, m, s_dev, n0, fold_u_host, fold_m, out_l_dev, out_r_dev);
 }
 int pc_hip_ec_fold(pc_ctx* ctx, pc_srs* srs, size_t n_half, const void* u_host) {
   if (!ctx || !srs || srs->ctx != ctx || !u_host || 2 * n_half > srs->n) return PC_ERR_INVALID_ARG;

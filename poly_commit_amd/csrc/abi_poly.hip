@@ -4,15 +4,9 @@
 #include <thread>
 #include <stdio.h>
 #include <string.h>
-#include "abi.hpp"
+#include "abi_fr.hpp"
 
 using pc::NttRunner;
-
-// the time between the two marks of a call that set exactly two (pc_hip_last_ntt_phases_ms)
-static void one_bracket(pc_ctx* ctx) {
-  ctx->ntt_phases[0] = ctx->ntt_phases[1] = 0;
-  if (ctx->be.timing && ctx->be.n_ev >= 2) (void)hipEventElapsedTime(&ctx->ntt_phases[0], ctx->be.ev[0], ctx->be.ev[1]);
-}
 
 // the context's NTT plan of 2^log_n points over one field, made on first use
 static NttRunner* ntt_plan(pc_ctx* ctx, pc_curve field_of, unsigned log_n) {
@@ -386,43 +380,8 @@ int pc_hip_matrix_columns(pc_ctx* ctx, const void* mat_dev, size_t rows, size_t 
 
 int pc_hip_fr_lincomb(pc_ctx* ctx, pc_curve field_of, const void* const* polys, pc_mem where_in, const size_t* lens,
                       size_t k, const void* xi_host, void* out, pc_mem where_out, size_t n_out) {
-  if (!ctx || !pc_known_curve(field_of) || (k && (!polys || !lens || !xi_host)) || (n_out && !out))
-    return PC_ERR_INVALID_ARG;
-  if (n_out >= (1ull << 32) || k >= (1ull << 20)) return PC_ERR_TOO_LARGE;
-  size_t total = 0;
-  for (size_t j = 0; j < k; j++) {
-    if (lens[j] >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-    if (lens[j] && !polys[j]) return PC_ERR_INVALID_ARG;
-    total += lens[j];
-  }
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    if (!n_out) return (int)PC_OK;
-    // host polynomials are staged back to back in one device buffer
-    Staged stage(ctx->be, nullptr, PC_MEM_HOST, where_in == PC_MEM_HOST ? total * 32 : 0, false, 0);
-    std::vector<uint64_t> addr(k ? k : 1, 0); std::vector<uint32_t> len32(k ? k : 1, 0);
-    size_t off = 0;
-    for (size_t j = 0; j < k; j++) {
-      len32[j] = (uint32_t)lens[j];
-      if (where_in == PC_MEM_HOST) {
-        if (lens[j]) ctx->be.copy_h2d((char*)stage.dev + off * 32, polys[j], lens[j] * 32);
-        addr[j] = (uint64_t)(uintptr_t)((char*)stage.dev + off * 32); off += lens[j];
-      } else addr[j] = (uint64_t)(uintptr_t)polys[j];
-    }
-    // the three small argument arrays side by side in the context's grow-only scratch (three hipMalloc / hipFree pairs per call before)
-    const size_t kk = k ? k : 1, o_len = kk * 8, o_xi = (o_len + kk * 4 + 31) & ~(size_t)31;
-    char* args = (char*)ctx->be.workspace(o_xi + kk * 32);
-    ctx->be.copy_h2d(args, addr.data(), kk * 8);
-    ctx->be.copy_h2d(args + o_len, len32.data(), kk * 4);
-    if (k) ctx->be.copy_h2d(args + o_xi, xi_host, k * 32);
-    Staged sout(ctx->be, out, where_out, n_out * 32, false, 1);
-    ctx->be.n_ev = 0; ctx->be.mark();
-    pc::field_ops(field_of).fr_lincomb(ctx->be, args, args + o_len, args + o_xi, k, sout.dev, n_out);
-    ctx->be.mark();
-    if (where_out == PC_MEM_HOST) ctx->be.copy_d2h(out, sout.dev, n_out * 32); else ctx->be.sync();
-    one_bracket(ctx);
-    return (int)PC_OK;
-  });
+  if (!pc_known_curve(field_of)) return PC_ERR_INVALID_ARG;
+  return fr_lincomb_call(ctx, pc::field_ops(field_of), polys, where_in, lens, k, xi_host, out, where_out, n_out);
 }
 
 }  // extern "C"

@@ -3,57 +3,34 @@
 // key range (hyrax/mod.rs:233-242).  This unit also instantiates everything templated on TeOf<T>
 // (te.hpp, MsmPlan<TeOf<T>, HipBackend> with the digit and sort stages of its scalar field), and nothing of a short Weierstrass group.
 #include <vector>
-#include "abi.hpp"
-#include "hip_backend_msm.hpp"
-#include "te.hpp"
+#include "abi_te.hpp"
+#include "blocking_lane.hpp"
 
 namespace pc {
 namespace {
 
-typedef TeOf<pc_te_ed_on_bls12_381> TeC;
-typedef TeC::FrP TeFrP;
-constexpr int TE_AW = AffD<TeC>::WORDS, TE_XY = AffD<TeC>::XY_WORDS, TE_XW = XyzzD<TeC>::WORDS, TE_FR_W = TeFrP::N, TE_FQ_W = TeC::FqP::N;
-constexpr size_t TE_POINT_BYTES = (size_t)TE_XY * 4;      // the caller's x || y
-constexpr uint32_t TE_NORM_K = 16;                        // points per inversion of the fold's normalisation (JacBatchAffineBody's default)
-
-// One blocking MSM pipeline: plain launches (no captured graphs), host scalars staged whole (no parts).  subs == 0: the table-free
-// single MSM; subs == B: the many-MSM pass against cfg's window table (`run` then takes B x m scalars and writes B points)
-struct TeRunnerT : TeRunner {
-  HipBackend& be;
-  MsmPlan<TeC, HipBackend> plan;
-  TeRunnerT(HipBackend& b, size_t n_max, const MsmConfig& cfg, uint32_t subs = 0) : be(b), plan(b, n_max, cfg, subs) {}
-  void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) override {
-    const uint32_t* sdev = (const uint32_t*)scalars;
-    be.n_ev = 0; be.mark();
-    if (where == PC_MEM_HOST) { be.copy_h2d(plan.scalar_staging(), scalars, n * (size_t)TE_FR_W * 4); sdev = plan.scalar_staging(); }
-    plan.run(bases, base_off, sdev, n, from_mont, out_host);
-  }
-  void shape(uint32_t out[4]) const override {
-    const MsmGeom& g = plan.last_geom();
-    out[0] = g.c; out[1] = g.Wd; out[2] = g.NB; out[3] = g.tbl_stride ? 1u : 0u;
-  }
-};
-
 // The window table of the m resident points at b0 (te.hpp) on the context's queue, the doubled rows staged in its workspace.  Returns
 // with the queue drained.
 void te_window_table_sync(HipBackend& be, const uint32_t* b0, size_t m, uint32_t c, uint32_t Wd, uint32_t* table) {
-  uint32_t* ext = (uint32_t*)be.workspace(m * (size_t)(TE_XW + TE_FQ_W) * 4);
-  te_window_table<TeC>(be, b0, m, c, Wd, table, ext, ext + m * (size_t)TE_XW, TE_NORM_K);
+  const TeNormBuf ws = te_norm_buf(be, m);
+  te_window_table<TeC>(be, b0, m, c, Wd, table, ws.ext, ws.scratch, TE_NORM_K);
   be.sync();
 }
 
-TeLane* te_lane(pc_te_srs* k) {
+// the key's own pipeline: the table-free single MSM, created on first use
+BlockingLane* te_lane(pc_te_srs* k) {
   if (k->lane) return k->lane;
-  TeLane* L = new TeLane();
-  try {
-    L->be.init();
-    MsmConfig cfg = k->ctx->msm_cfg;
-    cfg.tbl = nullptr; cfg.tbl_c = 0;
-    cfg.coop2_max_points = 0;      // one lane per point in every cooperative level (the two-lane form is an XYZZ schedule)
-    L->runner = new TeRunnerT(L->be, k->n, cfg);
-  } catch (...) { delete L; throw; }
-  k->lane = L;
-  return L;
+  MsmConfig cfg = k->ctx->msm_cfg;
+  cfg.tbl = nullptr; cfg.tbl_c = 0;
+  return k->lane = blocking_lane<TeC>(k->n, cfg, 0);
+}
+
+// the call's MSM on lane L, then what pc_hip_last_msm_shape and pc_hip_last_msm_phases_ms read
+void te_run(pc_ctx* ctx, BlockingLane* L, const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, pc_scalar_form form,
+            uint32_t* out) {
+  L->be.timing = ctx->be.timing;
+  L->runner->run(bases, base_off, scalars, where, n, form == PC_SCALARS_MONTGOMERY, out);
+  lane_phases(ctx, L);
 }
 
 void write_identity(uint32_t* out_xy) {
@@ -68,8 +45,6 @@ using pc::TE_AW;
 using pc::TE_XY;
 using pc::TE_POINT_BYTES;
 
-static int te_curve_check(pc_te_curve curve) { return curve == PC_TE_ED_ON_BLS12_381 ? PC_OK : PC_ERR_INVALID_ARG; }
-
 extern "C" {
 
 int pc_hip_te_srs_upload(pc_ctx* ctx, pc_te_curve curve, const void* bases, size_t n, size_t stride_bytes, pc_mem where, pc_te_srs** out) {
@@ -80,12 +55,7 @@ int pc_hip_te_srs_upload(pc_ctx* ctx, pc_te_curve curve, const void* bases, size
   if (stride_bytes < TE_POINT_BYTES) return PC_ERR_INVALID_ARG;
   if (n >= (1ull << 31)) return PC_ERR_TOO_LARGE;
   if (where == PC_MEM_DEVICE && stride_bytes != TE_POINT_BYTES) return PC_ERR_UNSUPPORTED;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  *out = nullptr;
-  pc_te_srs* k = nullptr;
-  int rc = guarded(ctx, [&]() {
-    k = te_key_create(ctx, curve, n, (size_t)TE_AW * 4);
-    if (!k) return (int)PC_ERR_OOM;
+  return key_make(ctx, out, [&]() { return te_key_create(ctx, curve, n, (size_t)TE_AW * 4); }, te_key_free, [&](pc_te_srs* k) {
     if (!n) return (int)PC_OK;
     // the caller's points, packed (twisted_edwards::Affine has no flag behind its coordinates: a larger stride is only skipped)
     std::vector<uint8_t> packed;
@@ -101,9 +71,6 @@ int pc_hip_te_srs_upload(pc_ctx* ctx, pc_te_curve curve, const void* bases, size
     ctx->be.sync();
     return (int)PC_OK;
   });
-  if (rc != PC_OK) { if (k) te_key_free(k); return rc; }
-  *out = k;
-  return PC_OK;
 }
 
 void pc_hip_te_srs_free(pc_te_srs* k) { key_free_locked(k, te_key_free); }
@@ -147,14 +114,8 @@ int pc_hip_te_msm(pc_ctx* ctx, const pc_te_srs* kc, size_t base_offset, const vo
   }
   std::lock_guard<std::recursive_mutex> lk(ctx->mu);
   return guarded(ctx, [&]() {
-    TeLane* L = pc::te_lane(k);
-    L->be.timing = ctx->be.timing;
-    L->runner->run(k->bases, (uint32_t)base_offset, scalars, where, n, form == PC_SCALARS_MONTGOMERY, (uint32_t*)out_xy);
-    L->runner->shape(ctx->shape);      // (pc_hip_last_msm_shape)
+    pc::te_run(ctx, pc::te_lane(k), k->bases, (uint32_t)base_offset, scalars, where, n, form, (uint32_t*)out_xy);
     if (out_is_identity) *out_is_identity = pc::host64::te_is_identity<pc_te_ed_on_bls12_381>((const uint32_t*)out_xy) ? 1 : 0;
-    // phase brackets of the call (pc_hip_last_msm_phases_ms), as for a G1 pipeline
-    for (int i = 0; i < 8; i++) ctx->phases[i] = 0;
-    if (L->be.timing) for (int i = 0; i + 1 < L->be.n_ev && i < 8; i++) (void)hipEventElapsedTime(&ctx->phases[i], L->be.ev[i], L->be.ev[i + 1]);
     return (int)PC_OK;
   });
 }
@@ -180,27 +141,19 @@ int pc_hip_te_msm_many(pc_ctx* ctx, pc_te_srs* k, size_t base_offset, const void
       te_drop_many(k);
       const size_t bytes = (size_t)Wd * m * (size_t)TE_AW * 4;
       uint32_t* table = (uint32_t*)ctx->be.alloc(bytes);
-      TeLane* L = nullptr;
+      BlockingLane* L = nullptr;
       try {
         pc::te_window_table_sync(ctx->be, k->bases + base_offset * (size_t)TE_AW, m, c, Wd, table);
-        L = new TeLane();
-        L->be.init();
         pc::MsmConfig cfg = ctx->msm_cfg;
         cfg.c = 0; cfg.T = 0; cfg.tbl = table; cfg.tbl_c = c; cfg.tbl_stride = (uint32_t)m; cfg.tbl_pt_stride = (uint32_t)TE_AW; cfg.tbl_min_n = 0;
         cfg.tbl_glv = false;
-        cfg.coop2_max_points = 0;      // one lane per point in every cooperative level, as for the single MSM
-        L->runner = new pc::TeRunnerT(L->be, n_msms * m, cfg, (uint32_t)n_msms);
-      } catch (...) { (void)hipStreamSynchronize(ctx->be.stream); delete L; ctx->be.free(table); throw; }
+        L = pc::blocking_lane<TeC>(n_msms * m, cfg, (uint32_t)n_msms);
+      } catch (...) { (void)hipStreamSynchronize(ctx->be.stream); ctx->be.free(table); throw; }
       M.table = table; M.table_bytes = bytes; M.lane = L; M.base_offset = base_offset; M.m = m; M.B = n_msms;
     }
-    TeLane* L = M.lane;
-    L->be.timing = ctx->be.timing;
-    L->runner->run(k->bases, 0, scalars, where, n_msms * m, form == PC_SCALARS_MONTGOMERY, out);
-    L->runner->shape(ctx->shape);
+    pc::te_run(ctx, M.lane, k->bases, 0, scalars, where, n_msms * m, form, out);
     if (out_is_identity)
       for (size_t i = 0; i < n_msms; i++) out_is_identity[i] = pc::host64::te_is_identity<pc_te_ed_on_bls12_381>(out + i * (size_t)TE_XY) ? 1 : 0;
-    for (int i = 0; i < 8; i++) ctx->phases[i] = 0;
-    if (L->be.timing) for (int i = 0; i + 1 < L->be.n_ev && i < 8; i++) (void)hipEventElapsedTime(&ctx->phases[i], L->be.ev[i], L->be.ev[i + 1]);
     return (int)PC_OK;
   });
 }
@@ -215,15 +168,13 @@ int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* k, size_t n_half, const void* u_ho
     te_drop_many(k);             // ... and the window table of its many-MSM pass
     k->in_subgroup = -1;
     // the sums in extended coordinates, then the prefix products of the normalisation
-    uint32_t* ext = (uint32_t*)be.workspace(n_half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);
-    uint32_t* scratch = ext + n_half * (size_t)pc::TE_XW;
+    const pc::TeNormBuf ws = pc::te_norm_buf(be, n_half);
     pc::TeEcFoldBody<TeC> f;
-    f.key = k->bases; f.half = (uint32_t)n_half; f.ext = ext;
+    f.key = k->bases; f.half = (uint32_t)n_half; f.ext = ws.ext;
     const pc::Fd<pc::TeFrP> u = pc::Fd<pc::TeFrP>::load((const uint32_t*)u_host).from_mont();
     f.naf.from_scalar(u.l);
     be.launch(f, n_half);
-    pc::TeBatchAffineBody<TeC> nb{ext, scratch, k->bases, (uint32_t)n_half, pc::TE_NORM_K};
-    be.launch(nb, (n_half + pc::TE_NORM_K - 1) / pc::TE_NORM_K);
+    pc::te_normalise(be, ws.ext, ws.scratch, k->bases, n_half);
     be.sync();
     return (int)PC_OK;
   });
@@ -231,36 +182,26 @@ int pc_hip_te_ec_fold(pc_ctx* ctx, pc_te_srs* k, size_t n_half, const void* u_ho
 
 int pc_hip_te_ec_fold_from(pc_ctx* ctx, const pc_te_srs* src, size_t n_half, const void* u_host, pc_te_srs** out) {
   if (!ctx || !src || src->ctx != ctx || !u_host || !out || !n_half || 2 * n_half > src->n) return PC_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  *out = nullptr;
-  pc_te_srs* dst = nullptr;
-  int rc = guarded(ctx, [&]() {
-    dst = te_key_create(ctx, src->te_curve, n_half, (size_t)TE_AW * 4);
-    if (!dst) return (int)PC_ERR_OOM;
+  return key_make(ctx, out, [&]() { return te_key_create(ctx, src->te_curve, n_half, (size_t)TE_AW * 4); }, te_key_free, [&](pc_te_srs* dst) {
     pc::HipBackend& be = ctx->be;
-    uint32_t* ext = (uint32_t*)be.workspace(n_half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);
-    uint32_t* scratch = ext + n_half * (size_t)pc::TE_XW;
+    const pc::TeNormBuf ws = pc::te_norm_buf(be, n_half);
     pc::NafMasks<pc::TE_FR_W> naf;
     naf.from_scalar(pc::Fd<pc::TeFrP>::load((const uint32_t*)u_host).from_mont().l);
     // from the key's table when it has one for this half and every digit of u has a row; the ladder otherwise: the same points
     pc::TeTableFoldBody<TeC> t;
     if (src->fold_tbl && 2 * n_half == src->n && t.dg.from_naf(naf, src->fold_rows)) {
-      t.key = src->bases; t.tbl = src->fold_tbl; t.half = (uint32_t)n_half; t.ext = ext;
+      t.key = src->bases; t.tbl = src->fold_tbl; t.half = (uint32_t)n_half; t.ext = ws.ext;
       be.launch(t, n_half);
     } else {
       pc::TeEcFoldBody<TeC> f;
-      f.key = src->bases; f.half = (uint32_t)n_half; f.ext = ext; f.naf = naf;
+      f.key = src->bases; f.half = (uint32_t)n_half; f.ext = ws.ext; f.naf = naf;
       be.launch(f, n_half);
     }
-    pc::TeBatchAffineBody<TeC> nb{ext, scratch, dst->bases, (uint32_t)n_half, pc::TE_NORM_K};
-    be.launch(nb, (n_half + pc::TE_NORM_K - 1) / pc::TE_NORM_K);
+    pc::te_normalise(be, ws.ext, ws.scratch, dst->bases, n_half);
     be.sync();
     if (src->in_subgroup == 1) dst->in_subgroup = 1;      // sums of multiples of subgroup points
     return (int)PC_OK;
   });
-  if (rc != PC_OK) { if (dst) te_key_free(dst); return rc; }
-  *out = dst;
-  return PC_OK;
 }
 
 int pc_hip_te_srs_precompute_fold(pc_ctx* ctx, pc_te_srs* k) {
@@ -278,16 +219,14 @@ int pc_hip_te_srs_precompute_fold(pc_ctx* ctx, pc_te_srs* k) {
       ctx->last_error = "fold table of " + std::to_string(need >> 20) + " MiB exceeds the allowed share of the free device memory";
       return (int)PC_ERR_UNSUPPORTED;
     }
-    uint32_t* ext = (uint32_t*)be.workspace(half * (size_t)(pc::TE_XW + pc::TE_FQ_W) * 4);
-    uint32_t* scratch = ext + half * (size_t)pc::TE_XW;
+    const pc::TeNormBuf ws = pc::te_norm_buf(be, half);
     uint32_t* tbl = (uint32_t*)be.alloc(need);
     try {
       be.copy_d2d(tbl, k->bases + row_words, row_words * 4);      // row 0: the upper half as it is
       for (uint32_t b = 0; b + 1 < pc::TE_FOLD_ROWS; b++) {     // row b + 1: one batched doubling of row b, normalised
-        pc::TeDblRowBody<TeC> d{tbl + b * row_words, ext};
+        pc::TeDblRowBody<TeC> d{tbl + b * row_words, ws.ext};
         be.launch(d, half);
-        pc::TeBatchAffineBody<TeC> nb{ext, scratch, tbl + (b + 1) * row_words, (uint32_t)half, pc::TE_NORM_K};
-        be.launch(nb, (half + pc::TE_NORM_K - 1) / pc::TE_NORM_K);
+        pc::te_normalise(be, ws.ext, ws.scratch, tbl + (b + 1) * row_words, half);
       }
       be.sync();
     } catch (...) { (void)hipStreamSynchronize(be.stream); be.free(tbl); throw; }

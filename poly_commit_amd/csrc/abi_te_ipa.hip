@@ -1,112 +1,52 @@
 // C ABI of the gfx950 backend (include/pc_hip.h): InnerProductArgPC::open over ed_on_bls12_381 (JubJub) on the device -- the vector
 // kernels of the halving rounds over the curve's 252-bit scalar field, and the rounds as one call (ipa_pc/mod.rs:664-711).
 // With them the two vector kernels of HyraxPC::open over that field, fr_lincomb and fr_dot (hyrax/mod.rs:347,356,391).
-// This unit instantiates the members of FieldOpsImpl that the rounds and Hyrax need for that field and no other: its 2-adicity is 1, there is
-// no NTT over it (and nothing of a FieldOps table: pc_curve keeps its four ids).  The group side is abi_te.hip's, through the C ABI.
+// This unit instantiates the FrVecOps part of FieldOpsImpl for that field (vec_table(): what the rounds and Hyrax need) and no other
+// member: its 2-adicity is 1, there is no NTT over it (and no FieldOps table: pc_curve keeps its four ids).  The entry points over the
+// table are abi_fr.hpp's, shared with the pc_curve fields.  The group side is abi_te.hip's, through the C ABI.
 #include <chrono>
 #include <string.h>
-#include "abi.hpp"
+#include "abi_fr.hpp"
+#include "abi_te.hpp"
 #include "field_ops_impl.hpp"
-#include "host_tail.hpp"
-#include "te_constants.h"
 
-namespace {
-typedef pc_ed_on_bls12_381_fr TeFrP;
-typedef pc::FieldOpsImpl<TeFrP> TeFr;
-typedef pc::host64::F64<TeFrP> TeFr64;
-constexpr size_t TE_POINT_BYTES = 2 * (size_t)pc_te_ed_on_bls12_381::FqP::N * 4, TE_FR_BYTES = (size_t)TeFrP::N * 4;
-int te_curve_check(pc_te_curve curve) { return curve == PC_TE_ED_ON_BLS12_381 ? PC_OK : PC_ERR_INVALID_ARG; }
-}  // namespace
+namespace pc {
+const FrVecOps& fr_vec_ops_ed_on_bls12_381() { static const FrVecOps t = FieldOpsImpl<TeFrP>::vec_table(); return t; }
+}  // namespace pc
+
+using pc::TE_POINT_BYTES;
+using pc::TE_FR_BYTES;
+typedef pc::host64::F64<pc::TeFrP> TeFr64;
 
 extern "C" {
 
 int pc_hip_te_fr_powers(pc_ctx* ctx, pc_te_curve curve, const void* z_host, size_t n, void* out_dev) {
-  if (!ctx || !z_host || (n && !out_dev)) return PC_ERR_INVALID_ARG;
   if (int rc = te_curve_check(curve)) return rc;
-  if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    if (n) TeFr::fr_powers(ctx->be, (const uint32_t*)z_host, n, (uint32_t*)out_dev);
-    return (int)PC_OK;
-  });
+  return fr_powers_call(ctx, pc::fr_vec_ops_ed_on_bls12_381(), z_host, n, out_dev);
 }
 
 // <a, b> and sum_j xi[j] * polys[j] over the curve's scalar field: HyraxPC::open's <lt, r> and t.row_mul(l) (hyrax/mod.rs:347,356,391)
 int pc_hip_te_fr_dot(pc_ctx* ctx, pc_te_curve curve, const void* a_dev, const void* b_dev, size_t n, void* out_host) {
-  if (!ctx || !out_host || (n && (!a_dev || !b_dev))) return PC_ERR_INVALID_ARG;
   if (int rc = te_curve_check(curve)) return rc;
-  if (n >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    TeFr::fr_dot(ctx->be, (const uint32_t*)a_dev, (const uint32_t*)b_dev, n, (uint32_t*)out_host);
-    return (int)PC_OK;
-  });
+  return fr_dot_call(ctx, pc::fr_vec_ops_ed_on_bls12_381(), a_dev, b_dev, n, out_host);
 }
 
 int pc_hip_te_fr_lincomb(pc_ctx* ctx, pc_te_curve curve, const void* const* polys, pc_mem where_in, const size_t* lens,
                          size_t k, const void* xi_host, void* out, pc_mem where_out, size_t n_out) {
-  if (!ctx || (k && (!polys || !lens || !xi_host)) || (n_out && !out)) return PC_ERR_INVALID_ARG;
   if (int rc = te_curve_check(curve)) return rc;
-  if (n_out >= (1ull << 32) || k >= (1ull << 20)) return PC_ERR_TOO_LARGE;
-  size_t total = 0;
-  for (size_t j = 0; j < k; j++) {
-    if (lens[j] >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-    if (lens[j] && !polys[j]) return PC_ERR_INVALID_ARG;
-    total += lens[j];
-  }
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    if (!n_out) return (int)PC_OK;
-    // host vectors are staged back to back in one device buffer; the three small argument arrays side by side in the context's scratch
-    Staged stage(ctx->be, nullptr, PC_MEM_HOST, where_in == PC_MEM_HOST ? total * TE_FR_BYTES : 0, false, 0);
-    std::vector<uint64_t> addr(k ? k : 1, 0); std::vector<uint32_t> len32(k ? k : 1, 0);
-    size_t off = 0;
-    for (size_t j = 0; j < k; j++) {
-      len32[j] = (uint32_t)lens[j];
-      if (where_in == PC_MEM_HOST) {
-        if (lens[j]) ctx->be.copy_h2d((char*)stage.dev + off * TE_FR_BYTES, polys[j], lens[j] * TE_FR_BYTES);
-        addr[j] = (uint64_t)(uintptr_t)((char*)stage.dev + off * TE_FR_BYTES); off += lens[j];
-      } else addr[j] = (uint64_t)(uintptr_t)polys[j];
-    }
-    const size_t kk = k ? k : 1, o_len = kk * 8, o_xi = (o_len + kk * 4 + 31) & ~(size_t)31;
-    char* args = (char*)ctx->be.workspace(o_xi + kk * TE_FR_BYTES);
-    ctx->be.copy_h2d(args, addr.data(), kk * 8);
-    ctx->be.copy_h2d(args + o_len, len32.data(), kk * 4);
-    if (k) ctx->be.copy_h2d(args + o_xi, xi_host, k * TE_FR_BYTES);
-    Staged sout(ctx->be, out, where_out, n_out * TE_FR_BYTES, false, 1);
-    TeFr::fr_lincomb(ctx->be, args, args + o_len, args + o_xi, k, sout.dev, n_out);
-    if (where_out == PC_MEM_HOST) ctx->be.copy_d2h(out, sout.dev, n_out * TE_FR_BYTES); else ctx->be.sync();
-    return (int)PC_OK;
-  });
+  return fr_lincomb_call(ctx, pc::fr_vec_ops_ed_on_bls12_381(), polys, where_in, lens, k, xi_host, out, where_out, n_out);
 }
 
 int pc_hip_te_ipa_fold_dots(pc_ctx* ctx, pc_te_curve curve, void* coeffs_dev, void* z_dev, size_t m, const void* u_host, const void* u_inv_host,
                             void* out_dots_host) {
-  if (!ctx || !coeffs_dev || !z_dev || !out_dots_host || !m || (m & (m - 1))) return PC_ERR_INVALID_ARG;
   if (int rc = te_curve_check(curve)) return rc;
-  if ((u_host != nullptr) != (u_inv_host != nullptr)) return PC_ERR_INVALID_ARG;
-  if (m >= (1ull << 31)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    TeFr::ipa_fold_dots(ctx->be, (uint32_t*)coeffs_dev, (uint32_t*)z_dev, m, (const uint32_t*)u_host, (const uint32_t*)u_inv_host, (uint32_t*)out_dots_host);
-    return (int)PC_OK;
-  });
+  return ipa_fold_dots_call(ctx, pc::fr_vec_ops_ed_on_bls12_381(), coeffs_dev, z_dev, m, u_host, u_inv_host, out_dots_host);
 }
 
 int pc_hip_te_ipa_key_scalars(pc_ctx* ctx, pc_te_curve curve, const void* coeffs_dev, size_t m, void* s_dev, size_t n0,
                               const void* fold_u_host, size_t fold_m, void* out_l_dev, void* out_r_dev) {
-  if (!ctx || !s_dev || !n0 || (n0 & (n0 - 1))) return PC_ERR_INVALID_ARG;
   if (int rc = te_curve_check(curve)) return rc;
-  if (fold_u_host && (fold_m < 2 || (fold_m & (fold_m - 1)) || fold_m > n0)) return PC_ERR_INVALID_ARG;
-  if ((out_l_dev != nullptr) != (out_r_dev != nullptr)) return PC_ERR_INVALID_ARG;
-  if (out_l_dev && (!coeffs_dev || m < 2 || (m & (m - 1)) || m > n0)) return PC_ERR_INVALID_ARG;
-  if (n0 >= (1ull << 32)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  return guarded(ctx, [&]() {
-    TeFr::ipa_key_scalars(ctx->be, (const uint32_t*)coeffs_dev, m, (uint32_t*)s_dev, n0, (const uint32_t*)fold_u_host, fold_m, (uint32_t*)out_l_dev,
-                          (uint32_t*)out_r_dev);
-    return (int)PC_OK;
-  });
+  return ipa_key_scalars_call(ctx, pc::fr_vec_ops_ed_on_bls12_381(), coeffs_dev, m, s_dev, n0, fold_u_host, fold_m, out_l_dev, out_r_dev);
 }
 
 // The halving loop of InnerProductArgPC::open as ONE call, in the order pc_hip_ipa_open_rounds runs it for the pc_curve curves: plain

@@ -2,15 +2,11 @@
 // sample_generators (ipa_pc/mod.rs:302-325) as a new resident key, and trim's prefix of a key (:384).  The kernels are te_setup.hpp's
 // (digest, from_random_bytes, cofactor: one lane per index) and te.hpp's batch normalisation; the key object is key.hpp's.
 #include <vector>
-#include "abi.hpp"
+#include "abi_te.hpp"
 #include "te_setup.hpp"
 
-namespace {
-typedef pc::TeOf<pc_te_ed_on_bls12_381> TeC;
-constexpr int TE_AW = pc::AffD<TeC>::WORDS, TE_XW = pc::XyzzD<TeC>::WORDS, TE_FQ_W = TeC::FqP::N;
-constexpr uint32_t TE_NORM_K = 16;      // points per inversion of the normalisation, as for the key fold (abi_te.hip)
-int te_curve_check(pc_te_curve curve) { return curve == PC_TE_ED_ON_BLS12_381 ? PC_OK : PC_ERR_INVALID_ARG; }
-}  // namespace
+using pc::TeC;
+using pc::TE_AW;
 
 extern "C" {
 
@@ -22,23 +18,16 @@ int pc_hip_te_sample_generators(pc_ctx* ctx, pc_te_curve curve, const void* prot
   if (!body.name.set(protocol_name, name_len)) return PC_ERR_INVALID_ARG;
   if ((uint64_t)count > ~(uint64_t)0 - first_index) return PC_ERR_INVALID_ARG;      // first_index + count leaves 64 bits
   if (count >= (1ull << 31)) return PC_ERR_TOO_LARGE;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  *out = nullptr;
-  pc_te_srs* k = nullptr;
-  int rc = guarded(ctx, [&]() {
-    k = te_key_create(ctx, curve, count, (size_t)TE_AW * 4);
-    if (!k) return (int)PC_ERR_OOM;
+  return key_make(ctx, out, [&]() { return te_key_create(ctx, curve, count, (size_t)TE_AW * 4); }, te_key_free, [&](pc_te_srs* k) {
     pc::HipBackend& be = ctx->be;
     // the points in extended coordinates | the prefix products of the normalisation | the digest counts | the flag of the cap
-    uint32_t* ext = (uint32_t*)be.workspace((count * (size_t)(TE_XW + TE_FQ_W + 1) + 1) * 4);
-    uint32_t* scratch = ext + count * (size_t)TE_XW;
-    uint32_t* digests = scratch + count * (size_t)TE_FQ_W;
+    const pc::TeNormBuf ws = pc::te_norm_buf(be, count, count + 1);
+    uint32_t* digests = ws.extra;
     uint32_t* failed = digests + count;
     be.memset(failed, 0, 4);
-    body.first = first_index; body.ext = ext; body.digests = digests; body.failed = failed;
+    body.first = first_index; body.ext = ws.ext; body.digests = digests; body.failed = failed;
     be.launch(body, count);
-    pc::TeBatchAffineBody<TeC> nb{ext, scratch, k->bases, (uint32_t)count, TE_NORM_K};
-    be.launch(nb, (count + TE_NORM_K - 1) / TE_NORM_K);
+    pc::te_normalise(be, ws.ext, ws.scratch, k->bases, count);
     uint32_t hit_cap = 0;
     be.copy_d2h(&hit_cap, failed, 4);
     if (hit_cap) {
@@ -49,27 +38,16 @@ int pc_hip_te_sample_generators(pc_ctx* ctx, pc_te_curve curve, const void* prot
     k->in_subgroup = 1;      // 8 * P in a group of order 8 r
     return (int)PC_OK;
   });
-  if (rc != PC_OK) { if (k) te_key_free(k); return rc; }
-  *out = k;
-  return PC_OK;
 }
 
 int pc_hip_te_srs_prefix(pc_ctx* ctx, const pc_te_srs* src, size_t count, pc_te_srs** out) {
   if (!ctx || !src || src->ctx != ctx || !out || !count || count > src->n) return PC_ERR_INVALID_ARG;
-  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-  *out = nullptr;
-  pc_te_srs* k = nullptr;
-  int rc = guarded(ctx, [&]() {
-    k = te_key_create(ctx, src->te_curve, count, (size_t)TE_AW * 4);
-    if (!k) return (int)PC_ERR_OOM;
+  return key_make(ctx, out, [&]() { return te_key_create(ctx, src->te_curve, count, (size_t)TE_AW * 4); }, te_key_free, [&](pc_te_srs* k) {
     ctx->be.copy_d2d(k->bases, src->bases, count * (size_t)TE_AW * 4);
     ctx->be.sync();
     if (src->in_subgroup == 1) k->in_subgroup = 1;
     return (int)PC_OK;
   });
-  if (rc != PC_OK) { if (k) te_key_free(k); return rc; }
-  *out = k;
-  return PC_OK;
 }
 
 }  // extern "C"

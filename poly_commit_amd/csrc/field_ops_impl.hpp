@@ -1,5 +1,5 @@
 // Instantiation of everything templated on one scalar field; each field_<name>.hip includes this header
-// and defines one FieldOps table (pc_internal.hpp).
+// and defines one FieldOps table (pc_internal.hpp); abi_te_ipa.hip includes it for the FrVecOps part alone.
 #pragma once
 #include <vector>
 #include "pc_internal.hpp"
@@ -123,8 +123,10 @@ struct FieldOpsImpl {
                                         const uint32_t* z, uint32_t* quot, const uint64_t* offs, uint32_t* ping, uint32_t* pong) {
     return pst13_divide<FrP>(be, table, T_host, n, d, p, z, quot, offs, ping, pong);
   }
+  static_assert(FrP::N * 4 == FR_BYTES, "abi_fr.hpp stages elements of FR_BYTES");
+  static FrVecOps vec_table() { return FrVecOps{&fr_dot, &ipa_fold_dots, &fr_powers, &ipa_key_scalars, &fr_lincomb}; }
   static FieldOps table() {
-    return FieldOps{&make_ntt, &poly_eval_f, &div_scan_f, &witness_f, &fr_fold, &fr_dot, &ipa_fold_dots, &fr_powers, &ipa_key_scalars, &fr_lincomb, &column_hash,
+    return FieldOps{vec_table(), &make_ntt, &poly_eval_f, &div_scan_f, &witness_f, &fr_fold, &column_hash,
                     &column_hash_part, &brakedown_encode_f, &brakedown_points<FrP>, &fold_tree_f, &div_multi_f,
                     &pst13_monomials_f, &pst13_write_f, &pst13_divide_f};
   }

@@ -212,8 +212,9 @@ inline MsmLane* new_lane(pc_curve curve, size_t capacity, const pc::MsmConfig& c
   return L;
 }
 
-// shape and phase brackets of the lane's last call (pc_hip_last_msm_shape, pc_hip_last_msm_phases_ms)
-inline void lane_phases(pc_ctx* ctx, MsmLane* L) {
+// shape and phase brackets of the lane's last call (pc_hip_last_msm_shape, pc_hip_last_msm_phases_ms); Lane: MsmLane or BlockingLane
+template <class Lane>
+inline void lane_phases(pc_ctx* ctx, Lane* L) {
   for (int i = 0; i < 8; i++) ctx->phases[i] = 0;
   L->runner->shape(ctx->shape);
   if (L->be.timing) for (int i = 0; i + 1 < L->be.n_ev && i < 8; i++) (void)hipEventElapsedTime(&ctx->phases[i], L->be.ev[i], L->be.ev[i + 1]);
@@ -483,17 +484,41 @@ inline size_t keys_bytes(const pc_ctx* ctx, size_t out[3]) {
   return ctx->keys.size();
 }
 
+// ---- blocking lanes --------------------------------------------------------------------------
+// One blocking MSM pipeline of a G2 or twisted Edwards key: own queue, own workspace, no job in flight between calls.  The unit of the
+// group makes it (blocking_lane.hpp); what needs no group is here.
+struct BlockingLane {
+  pc::HipBackend be;
+  pc::BlockingRunner* runner = nullptr;
+  ~BlockingLane() { delete runner; be.destroy(); }
+};
+inline size_t lane_bytes(const BlockingLane* L) { return L ? L->be.bytes_live : 0; }
+// pc_hip_ctx_trim's share: an idle pipeline gives its sort / scan scratch back
+inline void lane_trim(BlockingLane* L) { if (L) { L->be.sync(); L->be.trim(); } }
+
+// The frame of an entry point that hands out one new key or nothing: *out = null; under the context's lock and inside guarded(),
+// create() makes the key object (null: no host memory) and fill(k) writes its points (returns a status, may throw); on any failure the
+// key is freed again.  K: pc_g2_srs or pc_te_srs.
+template <class K, class Create, class Free, class Fill>
+inline int key_make(pc_ctx* ctx, K** out, Create create, Free free_key, Fill fill) {
+  *out = nullptr;
+  std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+  K* k = nullptr;
+  int rc = guarded(ctx, [&]() {
+    k = create();
+    return k ? (int)fill(k) : (int)PC_ERR_OOM;
+  });
+  if (rc != PC_OK) { if (k) free_key(k); return rc; }
+  *out = k;
+  return PC_OK;
+}
+
 // ---- G2 keys ---------------------------------------------------------------------------------
 // A key of G2 points (pc_hip_g2_srs_upload; MultilinearPC's powers_of_h and their pair sums): a type of its own, so that no G1 entry
 // point can be handed one.  Same rules as pc_srs: registered in its context, released with it (the host object then stays behind as a
 // tombstone with ctx == nullptr that pc_hip_g2_srs_free only deletes); one pipeline, created on first use by abi_g2.hip.
-struct G2Lane {
-  pc::HipBackend be;
-  pc::G2Runner* runner = nullptr;
-  ~G2Lane() { delete runner; be.destroy(); }
-};
 struct pc_g2_srs : pc_key_base {
-  G2Lane* lane = nullptr;
+  BlockingLane* lane = nullptr;
 };
 inline int g2_point_bytes(pc_curve c) { return 4 * fq_bytes(c); }
 
@@ -511,34 +536,26 @@ inline pc_g2_srs* g2_key_create(pc_ctx* ctx, pc_curve curve, size_t n) {
 // {bases, 0, 0, pipeline} bytes of one G2 key (the layout of key_bytes: G2 has no tables)
 inline void g2_key_bytes(const pc_g2_srs* k, size_t out[4]) {
   out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = out[2] = 0;
-  out[3] = k->lane ? k->lane->be.bytes_live : 0;
+  out[3] = lane_bytes(k->lane);
 }
 // pc_hip_shutdown's share
 inline void g2_keys_shutdown(pc_ctx* ctx) { key_registry_shutdown(ctx->g2_keys, g2_key_release_device); }
-// pc_hip_ctx_trim's share: an idle pipeline gives its sort / scan scratch back
-inline void g2_keys_trim(pc_ctx* ctx) {
-  for (pc_g2_srs* k : ctx->g2_keys) if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }
-}
+inline void g2_keys_trim(pc_ctx* ctx) { for (pc_g2_srs* k : ctx->g2_keys) lane_trim(k->lane); }
 
 // ---- twisted Edwards keys --------------------------------------------------------------------
 // A key of ed_on_bls12_381 points (pc_hip_te_srs_upload): a type of its own, as pc_g2_srs is, so that no short Weierstrass entry point can
 // be handed one -- its points have another law and no infinity.  Resident form: x || y || td with td = 2 d x y made at upload (te.hpp),
 // 3 Fq = 96 bytes a point, where the caller's is 64; `aw` counts the resident words, `curve` is unused.  Same rules as pc_g2_srs:
 // registered in its context, released with it (a tombstone stays behind), one pipeline, created on first use by abi_te.hip.
-struct TeLane {
-  pc::HipBackend be;
-  pc::TeRunner* runner = nullptr;
-  ~TeLane() { delete runner; be.destroy(); }
-};
 struct pc_te_srs : pc_key_base {
   pc_te_curve te_curve = PC_TE_ED_ON_BLS12_381;
-  TeLane* lane = nullptr;
+  BlockingLane* lane = nullptr;
   uint32_t* fold_tbl = nullptr;  // fold table (pc_hip_te_srs_precompute_fold): fold_rows rows of the n / 2 upper points and their doublings, or null
   uint32_t fold_rows = 0;
   int in_subgroup = -1;          // pc_hip_te_srs_in_subgroup's cached answer (-1: not asked yet)
   // many-MSM pass (pc_hip_te_msm_many), cached per shape as pc_srs::Many is: the window table of bases[base_offset .. base_offset + m)
   // (Wd rows of m resident records, from the context's allocator) and a pipeline of its own with B bucket sets
-  struct Many { size_t base_offset = 0, m = 0, B = 0; uint32_t* table = nullptr; size_t table_bytes = 0; TeLane* lane = nullptr; } many;
+  struct Many { size_t base_offset = 0, m = 0, B = 0; uint32_t* table = nullptr; size_t table_bytes = 0; BlockingLane* lane = nullptr; } many;
 };
 // the table and pipeline of the many-MSM pass go back: another shape is asked for, the key's points change (pc_hip_te_ec_fold), the key is released
 inline void te_drop_many(pc_te_srs* k) {
@@ -569,12 +586,7 @@ inline pc_te_srs* te_key_create(pc_ctx* ctx, pc_te_curve curve, size_t n, size_t
 // {bases, window table of the many-MSM pass, fold table, pipelines} bytes of one key (the layout of key_bytes)
 inline void te_key_bytes(const pc_te_srs* k, size_t out[4]) {
   out[0] = (k->n ? k->n : 1) * (size_t)k->aw * 4; out[1] = k->many.table_bytes; out[2] = te_fold_table_bytes(k);
-  out[3] = (k->lane ? k->lane->be.bytes_live : 0) + (k->many.lane ? k->many.lane->be.bytes_live : 0);
+  out[3] = lane_bytes(k->lane) + lane_bytes(k->many.lane);
 }
 inline void te_keys_shutdown(pc_ctx* ctx) { key_registry_shutdown(ctx->te_keys, te_key_release_device); }
-inline void te_keys_trim(pc_ctx* ctx) {
-  for (pc_te_srs* k : ctx->te_keys) {
-    if (k->lane) { k->lane->be.sync(); k->lane->be.trim(); }
-    if (k->many.lane) { k->many.lane->be.sync(); k->many.lane->be.trim(); }
-  }
-}
+inline void te_keys_trim(pc_ctx* ctx) { for (pc_te_srs* k : ctx->te_keys) { lane_trim(k->lane); lane_trim(k->many.lane); } }

@@ -5,12 +5,20 @@
 //                      srs (keys and their tables), msm, poly (polynomials, NTT, hashing, Ligero), ipa, lincode (the Brakedown code object),
 //                      skzg (streaming_kzg: folding tree, multi-point openings), pst13 (MarlinPST13: layout, commit, open); staging,
 //                      error translation
-//   key.hpp            host only: the key objects -- pc_key_base and what G1 and G2 keys share over it (fill, read-back, registry,
-//                      locked free), pc_srs with its pipelines and the derived keys of an opening, pc_g2_srs -- their whole lifetime
+//   key.hpp            host only: the key objects -- pc_key_base and what the keys of every group share over it (fill, read-back,
+//                      registry, locked free, key_make: one new key or nothing), pc_srs with its pipelines and the derived keys of an
+//                      opening, pc_g2_srs and pc_te_srs with their BlockingLane (residency, trim) -- their whole lifetime
 //   abi.hpp            host only: the staging helpers more than one abi unit uses
+//   abi_fr.hpp         host only: the entry points over a scalar field's vector kernels (FrVecOps below), written once for the fields
+//                      of pc_curve (abi_ipa.hip, abi_poly.hip) and for ed_on_bls12_381's (abi_te_ipa.hip)
 //   curve_<name>.hip   everything templated on one curve: MSM pipeline, window table, key fold, fixed-base mul, pair sums
 //   abi_g2.hip         beside its entry points, everything templated on G2 (BLS12-381 only); it instantiates no G1 kernel
-//   abi_te.hip         the same for the twisted Edwards group ed_on_bls12_381 (te.hpp): typed keys, MSM, key fold
+//   abi_te.hip         the same for the twisted Edwards group ed_on_bls12_381 (te.hpp): typed keys, MSM, many-MSM pass, key fold
+//   blocking_lane.hpp  the blocking MSM lane of those two groups (BlockingRunner below over MsmPlan<G, HipBackend>): one copy, included
+//                      by abi_g2.hip and abi_te.hip alone, each instantiating it for its own group
+//   abi_te.hpp         what the three twisted Edwards units share: the group's names and sizes, the id check, the normalisation tail
+//   abi_te_setup.hip   sample_generators and the prefix of a twisted Edwards key (te_setup.hpp)
+//   abi_te_ipa.hip     the FrVecOps table of ed_on_bls12_381's scalar field (no NTT, no FieldOps entry) and the opening as one call
 //   fixed_base.hpp     the group-generic launch sequences (fixed-base batch multiplication, pair sums): one copy, instantiated for
 //                      G1 by the curve units and for G2 by abi_g2.hip
 //   host_tail.hpp      host only: 64-bit-limb points of either group -- the MSM's Horner tail, affine -> XYZZ, one scalar
@@ -47,21 +55,13 @@ struct MsmRunner {
   virtual void trim() = 0;          // give back what can be rebuilt on demand (idle pipeline only)
 };
 
-// One G2 MSM pipeline (abi_g2.hip makes it: MsmPlan<G2Of<C>, HipBackend>, blocking, table-free)
-struct G2Runner {
-  virtual ~G2Runner() {}
-  // out_host: the affine sum, 4 Fq (all zero = infinity)
+// One blocking MSM pipeline of G2 or of the twisted Edwards group (blocking_lane.hpp: MsmPlan<G, HipBackend>; abi_g2.hip and abi_te.hip
+// each make their own group's)
+struct BlockingRunner {
+  virtual ~BlockingRunner() {}
+  // out_host: the affine sum(s) -- G2: 4 Fq (all zero = infinity); twisted Edwards: x || y, 2 Fq (the identity is (0, 1)), n >= 1
   virtual void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) = 0;
-  // geometry of the last run, as MsmRunner::shape reports it (out[3] = 0: the pipeline is table-free)
-  virtual void shape(uint32_t out[4]) const = 0;
-};
-
-// One twisted Edwards MSM pipeline (abi_te.hip makes it: MsmPlan<TeOf<T>, HipBackend>, blocking, table-free)
-struct TeRunner {
-  virtual ~TeRunner() {}
-  // n >= 1 pairs; out_host: the affine sum x || y, 2 Fq (the identity is (0, 1))
-  virtual void run(const uint32_t* bases, uint32_t base_off, const void* scalars, pc_mem where, size_t n, bool from_mont, uint32_t* out_host) = 0;
-  // geometry of the last run, as MsmRunner::shape reports it (out[3] = 0: the pipeline is table-free)
+  // geometry of the last run, as MsmRunner::shape reports it
   virtual void shape(uint32_t out[4]) const = 0;
 };
 
@@ -112,19 +112,25 @@ inline size_t skzg_div_scratch_bytes(size_t max_len, size_t count, uint32_t k) {
   return (2 * (max_len > SKZG_TILE ? max_len : 0) + count * k + k) * 32 + count * 24 + 64;
 }
 
-struct FieldOps {
-  NttRunner* (*make_ntt)(HipBackend& be, unsigned log_n);
-  void (*poly_eval)(HipBackend& be, const uint32_t* x, size_t n, const uint32_t* z_host, uint32_t* out_host, uint32_t fan);
-  void (*div_scan)(HipBackend& be, const uint32_t* x, size_t n, const uint32_t* z_host, const uint32_t* carry_in_host, uint32_t* out,
-                   uint32_t fan);
-  void (*witness)(HipBackend& be, const uint32_t* p, size_t n, const uint32_t* z_host, uint32_t* q, uint32_t fan);
-  void (*fr_fold)(HipBackend& be, uint32_t* lo, const uint32_t* hi, size_t n, const uint32_t* s);
+// The vector kernels of the IPA rounds and of Hyrax's opening: all that exists over a scalar field without an NTT (abi_te_ipa.hip
+// makes this table alone for ed_on_bls12_381's field, which has no pc_curve id; abi_fr.hpp holds the entry points over it)
+constexpr size_t FR_BYTES = 32;      // one element of any of the scalar fields here: 8 words (FieldOpsImpl asserts it)
+struct FrVecOps {
   void (*fr_dot)(HipBackend& be, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out_host);
   void (*ipa_fold_dots)(HipBackend& be, uint32_t* c, uint32_t* z, size_t m, const uint32_t* u_host, const uint32_t* u_inv_host, uint32_t* out_host);
   void (*fr_powers)(HipBackend& be, const uint32_t* z, size_t n, uint32_t* out);
   void (*ipa_key_scalars)(HipBackend& be, const uint32_t* c, size_t m, uint32_t* s, size_t n0, const uint32_t* fold_u, size_t fold_m,
                           uint32_t* out_l, uint32_t* out_r);
   void (*fr_lincomb)(HipBackend& be, const void* addr, const void* lens, const void* xi, size_t k, void* out, size_t n_out);
+};
+
+struct FieldOps : FrVecOps {
+  NttRunner* (*make_ntt)(HipBackend& be, unsigned log_n);
+  void (*poly_eval)(HipBackend& be, const uint32_t* x, size_t n, const uint32_t* z_host, uint32_t* out_host, uint32_t fan);
+  void (*div_scan)(HipBackend& be, const uint32_t* x, size_t n, const uint32_t* z_host, const uint32_t* carry_in_host, uint32_t* out,
+                   uint32_t fan);
+  void (*witness)(HipBackend& be, const uint32_t* p, size_t n, const uint32_t* z_host, uint32_t* q, uint32_t fan);
+  void (*fr_fold)(HipBackend& be, uint32_t* lo, const uint32_t* hi, size_t n, const uint32_t* s);
   void (*column_hash)(HipBackend& be, int hash, const uint32_t* ext, uint32_t rows, uint32_t n_cols, uint32_t* out);
   // one slab of rows absorbed into the per-column chaining states (hash.hpp, ColumnHashPartBody); columns [col0, col0 + cols)
   void (*column_hash_part)(HipBackend& be, int hash, const uint32_t* ext, uint32_t rows, uint32_t n_cols, uint32_t rows_total, uint32_t col0,
@@ -152,6 +158,7 @@ struct FieldOps {
 // device image, where the host function addresses do not exist)
 const CurveOps& curve_ops_bls12_381(); const CurveOps& curve_ops_bn254(); const CurveOps& curve_ops_pallas(); const CurveOps& curve_ops_bls12_377();
 const FieldOps& field_ops_bls12_381(); const FieldOps& field_ops_bn254(); const FieldOps& field_ops_pallas(); const FieldOps& field_ops_bls12_377();
+const FrVecOps& fr_vec_ops_ed_on_bls12_381();      // abi_te_ipa.hip
 
 // (the entry points have refused every id outside [0, PC_CURVE_LAST], curves.hpp, before they come here)
 inline const CurveOps& curve_ops(pc_curve c) {
