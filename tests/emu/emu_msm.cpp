@@ -212,6 +212,8 @@ static void run_many(const uint32_t* bases, size_t m, const uint32_t* scalars, s
 }
 static bool g_many_glv = false;      // emu_msm_many_vectors: the key's table is the GLV (half-scalar) one
 extern "C" void emu_set_many_glv(int on) { g_many_glv = on != 0; }
+static int g_many_chunk = 0;         // emu_msm_many_vectors: the key's chunk length (pc_hip_set_msm_tuning(0, T) reaches the batch passes through srs->cfg); 0 = the plan's own
+extern "C" void emu_set_many_chunk(int T) { g_many_chunk = T > 0 ? T : 0; }
 // the same with the scalar vectors in separate buffers and fewer vectors than bucket sets (pc_hip_msm_batch's fast path)
 template <class C>
 static void run_many_vectors(const uint32_t* bases, size_t n_srs, size_t base_off, size_t m, const uint32_t* const* vecs, size_t count, size_t B, int c,
@@ -222,7 +224,7 @@ static void run_many_vectors(const uint32_t* bases, size_t n_srs, size_t base_of
   std::vector<uint32_t> table((size_t)Wd * n_srs * AW);
   { pc::WindowTableBody<C> b{bases, (uint32_t)n_srs, (uint32_t)c, Wd, table.data(), (uint32_t)AW}; be.launch(b, n_srs); }
   pc::MsmConfig cfg; cfg.tbl = table.data(); cfg.tbl_c = (uint32_t)c; cfg.tbl_stride = (uint32_t)n_srs; cfg.tbl_pt_stride = AW; cfg.tbl_min_n = 1;
-  cfg.tbl_glv = g_many_glv;
+  cfg.tbl_glv = g_many_glv; cfg.T = (uint32_t)g_many_chunk;
   cfg.tbl_K0 = 4; cfg.K1 = 16; cfg.coop_max_points = 64; cfg.seg_tail_lanes = 3;
   pc::MsmPlan<C, CpuStepBackend> plan(be, B * m, cfg, (uint32_t)B);
   std::vector<uint64_t> ptrs(count);

@@ -745,3 +745,103 @@ def test_fold_table_one_and_two_levels(curve, levels, w):
     else:
         q = n // 4
         assert got == [R.ec_add(curve, k1[i], R.ec_mul(curve, u2, k1[q + i])) for i in range(q)]
+
+
+# ---- sums that become the point at infinity inside the pipeline (tests/harness/signedkey.py; the device runs tests/test_msm_cancel_gpu.py) ----
+def _cancel_rows(curve, m, start, seed):
+    """[random, const (cancels), copy of row 0, all_but_one] against key positions start .. start + m of signed(.., holes=True)"""
+    from harness import signedkey as SK
+    lay = SK.layouts(curve, m, seed, start, holes=True)
+    rnd = SK.rand_scalars(curve, m, seed + 1)
+    return [rnd, lay["const"], list(rnd), lay["all_but_one"]]
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_many_mode_stepped_rows_that_cancel_beside_rows_that_do_not(curve):
+    """Many-MSM mode, m = 40, B = 4, c = 6, on a key of P, -P neighbours with a hole: bucket set 1 holds nothing but sums that cancelled
+    (its row is the point at infinity, all-zero words), between sets 0 and 2 that hold the same finite sums, and set 3 one entry off
+    a cancelling row.  pc_hip_msm_many's form (one scalar matrix, the pass's own table) and the batch fast path's (separate vectors
+    over the key's table from an odd offset, plain and GLV form, fewer vectors than bucket sets); then ONE base under one scalar per
+    row, where every join of a row adds equal sums.  Expected: Python integers and one scalar multiplication."""
+    from harness import signedkey as SK
+    m, B, c = 40, 4, 6
+    nq = 2 * O.fq_limbs(curve)
+    key = SK.signed(curve, m, holes=True)
+    rows = _cancel_rows(curve, m, 0, 0xE40)
+    want = np.stack([SK.expected(key, r) for r in rows])
+    assert not want[1].any() and want[0].any() and want[3].any() and (want[0] == want[2]).all()
+    flat = SK.limbs([v for r in rows for v in r])
+    for K0 in (2, 0, 4):
+        out = np.ones((B, nq), dtype=np.uint64)
+        emu().emu_msm_many(O.CURVES[curve], p32(key.bases.view(np.uint32)), C.c_size_t(m), p32(flat.view(np.uint32)), C.c_size_t(B), c, K0, 0, p32(out.view(np.uint32)))
+        assert (out == want).all(), K0
+    one = SK.one_base(curve, m)
+    ks = [1, 3, SK.rand_scalars(curve, 1, 7)[0], 0]
+    eq = [[k] * m for k in ks]
+    out = np.ones((B, nq), dtype=np.uint64)
+    emu().emu_msm_many(O.CURVES[curve], p32(one.bases.view(np.uint32)), C.c_size_t(m), p32(SK.limbs([v for r in eq for v in r]).view(np.uint32)), C.c_size_t(B), c, 2, 0,
+                       p32(out.view(np.uint32)))
+    assert (out == np.stack([SK.expected(one, r) for r in eq])).all()
+    # separate vectors, the key's own table, base offset 7 (odd: the layouts are laid against positions 7 .. 47)
+    off = 7
+    big = SK.signed(curve, m + off, holes=True)
+    rows = _cancel_rows(curve, m, off, 0xE41)
+    want = np.stack([SK.expected(big, r, off) for r in rows])
+    assert not want[1].any() and want[3].any()
+    # (the chunk length of a batch pass is the key's: the context's tuning at upload; 1, 2 and 5 entries per lane as the device test sets them)
+    for glv, T in ((0, 0), (1, 0), (0, 1), (0, 2), (1, 5), (0, 5)):
+        for vecs in (rows, rows[1:3]):                                           # four vectors in four sets; two in four: the cancelling row first
+            mont = [SK.mont(curve, r) for r in vecs]
+            arr = (C.c_void_p * len(vecs))(*[v.ctypes.data for v in mont])
+            out = np.ones((B, nq), dtype=np.uint64)
+            emu().emu_set_many_glv(glv)
+            emu().emu_set_many_chunk(T)
+            try:
+                emu().emu_msm_many_vectors(O.CURVES[curve], p32(big.bases.view(np.uint32)), C.c_size_t(m + off), C.c_size_t(off), C.c_size_t(m), arr,
+                                           C.c_size_t(len(vecs)), C.c_size_t(B), c, 1, p32(out.view(np.uint32)))
+            finally:
+                emu().emu_set_many_glv(0)
+                emu().emu_set_many_chunk(0)
+            w = want if len(vecs) == 4 else want[1:3]
+            assert (out[:len(vecs)] == w).all(), (glv, T, len(vecs))
+            assert not out[len(vecs):].any()
+
+
+@pytest.mark.parametrize("curve", CURVES)
+def test_single_msm_stepped_on_cancelling_layouts(curve):
+    """The single MSM's stepped entries on the same key: table-free under chunks of 1, 2, 5 and 8 entries (an even chunk's partial sum
+    is the point at infinity and is written to its slot as such; odd chunks alternate +-k P and cancel in the joins), the window table
+    in its plain and GLV form (both halves of a pair's scalar split alike: both bucket sets cancel), and the MSM in parts on the
+    halves key, where every bucket of the later parts is the negative of the first part's and BucketMergeBody adds P and -P."""
+    from harness import signedkey as SK
+    n = 64
+    key = SK.signed(curve, n, holes=True)
+    lay = SK.layouts(curve, n, 0xE42, 0, holes=True)
+    for name in ("const", "pairwise", "pairwise_few", "all_but_one"):
+        s = SK.limbs(lay[name])
+        want = SK.expected(key, lay[name])
+        assert want.any() == (name == "all_but_one")
+        for (c, T, T2, K0) in ((4, 1, 4, 2), (6, 2, 4, 2), (5, 5, 5, 2), (7, 8, 4, 4), (0, 0, 0, 0)):
+            assert (run_msm(curve, key.bases, s, c, T, T2, K0) == want).all(), (name, c, T)
+        for c, K0 in ((4, 2), (7, 0)):
+            assert (run_msm_table(curve, key.bases, s, c, K0) == want).all(), (name, "table", c)
+            assert (run_msm_table_glv(curve, key.bases, s, c, K0) == want).all(), (name, "glv table", c)
+    un = SK.unsigned(curve, n)
+    opp = SK.layouts(curve, n, 0xE43)["opposite_scalars"]
+    assert not SK.expected(un, opp).any()
+    assert not run_msm(curve, un.bases, SK.limbs(opp), 5, 5, 4, 2).any()
+    # in parts: s[j] = s[j + n / 2] on halves(n)
+    n = 240
+    h = SK.halves(curve, n)
+    half = SK.rand_scalars(curve, n // 2, 0xE44)
+    one_off = half + half
+    one_off[n // 2 + 17] = (one_off[17] + 5) % SK.modulus(curve)
+    for s in (half + half, one_off):
+        want = SK.expected(h, s)
+        assert want.any() == (s is one_off)
+        for c, glv in ((7, 0), (9, 1), (0, 0)):
+            for parts in (2, 4):
+                out = np.ones(2 * O.fq_limbs(curve), dtype=np.uint64)
+                assert emu().emu_msm_parts(O.CURVES[curve], p32(h.bases.view(np.uint32)), C.c_size_t(n), p32(SK.limbs(s).view(np.uint32)), C.c_size_t(n), 0, c, glv,
+                                           parts, 0, p32(out.view(np.uint32))) == 0
+                assert (out == want).all(), (c, glv, parts)
