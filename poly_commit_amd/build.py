@@ -32,7 +32,8 @@ PROBE_OUT = os.path.join(PROBE_DIR, "libpc_probe.so")
 PROBE_UNITS = ([("probe_field.hip", k) for k in range(3)] + [("probe_curve.hip", k) for k in range(4)] +
                [("probe_halfadd.hip", k) for k in range(3)] + [("probe_fq30.hip", None), ("probe_chain30.hip", None)] +
                [("probe_field_bls12_377.hip", None), ("probe_curve_bls12_377.hip", None)] +
-               [("probe_field_te.hip", None), ("probe_te.hip", None), ("probe_te_setup.hip", None)])
+               [("probe_field_te.hip", None), ("probe_te.hip", None), ("probe_te_setup.hip", None)] +
+               [("probe_sort.hip", None)])
 # a unit whose source this tree's tests/hip does not have is left out: a tests/ tree from before the unit was added still builds its
 # probe, and a test that needs the unit fails at its missing entry point
 PROBE_UNITS = [u for u in PROBE_UNITS if os.path.exists(os.path.join(PROBE_DIR, u[0]))]

@@ -318,6 +318,7 @@ struct HipBackend {
   void* work_ws = nullptr; size_t work_ws_bytes = 0;
   void* stage_ws[2] = {nullptr, nullptr}; size_t stage_bytes[2] = {0, 0};
   int sort_mode = -1;   // -1 = read PC_HIP_SORT on first use; 0 = atomic; 1 = LDS radix
+  bool last_sort_atomic = false;   // which sort the last sort_entries call took (read by the test-only sort probe)
   bool tail_split = false; hipStream_t main_stream = nullptr, tail_stream = nullptr; hipEvent_t tail_ev = nullptr;
 
   // bucket accumulation with the neighbour merge of cut runs (msm_coop.hpp)

@@ -13,11 +13,11 @@ template <class C>
 void HipBackend::sort_entries(const MsmGeom& g, const uint32_t* scalars, uint32_t* hist, uint32_t* offsets, uint32_t* cursor,
                               uint32_t* entries) {
   if (sort_mode < 0) { const char* e = getenv("PC_HIP_SORT"); sort_mode = (e && !strcmp(e, "atomic")) ? 0 : 1; }
+  last_sort_atomic = true;
   if (sort_mode == 0) { sort_entries_atomic<C>(*this, g, scalars, hist, offsets, cursor, entries); return; }
   SortGeom sg = make_sort_geom(g, C::FrP::BITS);
-  if (sg.fine_bits > 11 || sg.NC > 16384) {   // wider than the fine pass's LDS histogram, or more bucket sets than the coarse one holds
-    sort_entries_atomic<C>(*this, g, scalars, hist, offsets, cursor, entries); return;
-  }
+  if (sort_needs_atomic(sg)) { sort_entries_atomic<C>(*this, g, scalars, hist, offsets, cursor, entries); return; }
+  last_sort_atomic = false;
   // workspace: G[nblocks][NC] | bintotal[NC+1] | binbase[NC+1] | records[n*W] (8 B each)
   const size_t gw = (size_t)sg.nblocks * sg.NC, nb1 = (size_t)sg.NC + 1;
   const size_t rec_off = ((gw + 2 * nb1) * 4 + 15) & ~(size_t)15;
@@ -29,7 +29,7 @@ void HipBackend::sort_entries(const MsmGeom& g, const uint32_t* scalars, uint32_
   }
   uint32_t* G = (uint32_t*)sort_ws; uint32_t* bintotal = G + gw; uint32_t* binbase = bintotal + nb1;
   uint2* records = (uint2*)((char*)sort_ws + rec_off);
-  const size_t lds = (size_t)sg.NC * 4;
+  const size_t lds = sort_pass_lds_bytes(sg);
   uint32_t* split = (uint32_t*)((char*)sort_ws + split_off);
   if constexpr (HasGlv<C>::value) if (g.glv) {      // k = k1 + k2 lambda once per scalar (Montgomery -> canonical fused): both passes below read the 40-byte records
     GlvPresplitBody<C> b{g, scalars, split};
@@ -49,8 +49,7 @@ void HipBackend::sort_entries(const MsmGeom& g, const uint32_t* scalars, uint32_
   // 512 workgroups cover the chip twice at most: with 256 lanes each that is 2 waves per SIMD for two passes that are bound
   // by DRAM latency (a scalar load, ~13 LDS atomics and as many 8-byte stores per lane and iteration).  16 waves per workgroup
   // give 8 per SIMD; the LDS histogram (<= 64 KiB) still allows two workgroups per CU.  PC_HIP_SORT_THREADS overrides (tuning).
-  static const int threads_env = []() { const char* e = getenv("PC_HIP_SORT_THREADS"); return e ? atoi(e) : 0; }();
-  const int sort_threads = threads_env ? threads_env : (lds > 32 * 1024 || g.n >= 65536) ? 1024 : 256;
+  const int sort_threads = sort_pass_threads(sg);
   pass(std::false_type{}, (const uint32_t*)nullptr, (uint2*)nullptr, sort_threads);
   mark();   // 1: digits + coarse histogram
   hipLaunchKernelGGL(k_sort_binscan, dim3((sg.NC + 15) / 16), dim3(256), 0, stream, G, sg.nblocks, sg.NC, bintotal);

@@ -875,6 +875,23 @@ inline uint32_t msm_choose_c(size_t n, uint32_t scalar_bits = 255) {
   return c;
 }
 
+// The geometry of a call of n pairs at window width c (MsmPlan::plan_geometry; the test-only sort probe makes its calls' geometry
+// here too).  tbl: against a window table of `tbl_stride` points per window (one shared bucket set, two with the GLV halves);
+// subs: that many bucket sets' worth of independent MSMs.  The per-call fields (base_off, from_mont, m_sub, scalar_tab, T) are
+// filled in by MsmPlan::part_body.
+inline MsmGeom msm_make_geom(uint32_t scalar_bits, size_t n, uint32_t c, bool tbl, bool glv, uint32_t subs, uint32_t tbl_stride,
+                             uint32_t pt_stride, uint32_t T2, uint32_t T2b) {
+  if (c < 2 || c > 24) throw std::runtime_error("MsmPlan: window width out of range (2..24)");   // ScalarDigits' shift register, the sort passes
+  MsmGeom g;
+  g.glv = glv ? 1u : 0u;
+  g.c = c; g.Wd = glv ? 2 * msm_num_windows(GLV_HALF_BITS, c) : msm_num_windows(scalar_bits, c);
+  g.W = subs ? subs * (glv ? 2u : 1u) : tbl ? (glv ? 2u : 1u) : g.Wd; g.tbl_stride = tbl ? tbl_stride : 0u; g.m_sub = 0;
+  g.nb_win = 1u << (c - 1); g.NB = g.W * g.nb_win;
+  g.pt_stride = pt_stride;
+  g.n = (uint32_t)n; g.base_off = 0; g.from_mont = 0; g.T = 0; g.T2 = T2; g.T2b = T2b; g.scalar_tab = nullptr;
+  return g;
+}
+
 template <class C, class Backend>
 class MsmPlan {
  public:
@@ -1211,14 +1228,7 @@ class MsmPlan {
   void plan_geometry(size_t n) {
     const bool tbl = subs_ || (cfg_.tbl && cfg_.tbl_c && n >= cfg_.tbl_min_n);
     uint32_t c = tbl ? cfg_.tbl_c : cfg_.c ? cfg_.c : msm_choose_c(n, FrP::BITS);
-    if (c < 2 || c > 24) throw std::runtime_error("MsmPlan: window width out of range (2..24)");   // ScalarDigits' shift register, the sort passes
-    const bool glv = tbl && cfg_.tbl_glv;
-    g_.glv = glv ? 1u : 0u;
-    g_.c = c; g_.Wd = glv ? 2 * msm_num_windows(GLV_HALF_BITS, c) : msm_num_windows(FrP::BITS, c);
-    g_.W = subs_ ? subs_ * (glv ? 2u : 1u) : tbl ? (glv ? 2u : 1u) : g_.Wd; g_.tbl_stride = tbl ? cfg_.tbl_stride : 0u; g_.m_sub = 0;
-    g_.nb_win = 1u << (c - 1); g_.NB = g_.W * g_.nb_win;
-    g_.pt_stride = tbl ? cfg_.tbl_pt_stride : (uint32_t)AW;
-    g_.n = (uint32_t)n; g_.base_off = 0; g_.from_mont = 0; g_.T = 0; g_.T2 = cfg_.T2; g_.T2b = cfg_.T2b; g_.scalar_tab = nullptr;
+    g_ = msm_make_geom(FrP::BITS, n, c, tbl, tbl && cfg_.tbl_glv, subs_, cfg_.tbl_stride, tbl ? cfg_.tbl_pt_stride : (uint32_t)AW, cfg_.T2, cfg_.T2b);
     uint32_t m = g_.nb_win; n_levels_ = 0;
     uint32_t kbits = 0; arr_exp_.clear();
     while (m > 1) {

@@ -62,6 +62,16 @@ inline SortGeom make_sort_geom(const MsmGeom& g, uint32_t scalar_bits) {
   return s;
 }
 
+// more fine buckets than k_sort_fine's LDS histogram holds, or more bucket sets than the coarse one does: HipBackend::sort_entries
+// takes the atomic sort
+inline bool sort_needs_atomic(const SortGeom& sg) { return sg.fine_bits > 11 || sg.NC > 16384; }
+inline size_t sort_pass_lds_bytes(const SortGeom& sg) { return (size_t)sg.NC * 4; }
+// lanes of the two coarse passes (PC_HIP_SORT_THREADS overrides; the reasons are at the call in sort_entries)
+inline int sort_pass_threads(const SortGeom& sg) {
+  static const int threads_env = []() { const char* e = getenv("PC_HIP_SORT_THREADS"); return e ? atoi(e) : 0; }();
+  return threads_env ? threads_env : (sort_pass_lds_bytes(sg) > 32 * 1024 || sg.n >= 65536) ? 1024 : 256;
+}
+
 // GLV: 0 plain scalars; 2 `scalars` is the pre-split array of k_glv_presplit (GLV_SPLIT_WORDS words per scalar, in call order:
 // sub-MSM addressing already resolved)
 template <class C, bool SCATTER, int GLV = 0>

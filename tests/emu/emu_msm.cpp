@@ -595,3 +595,27 @@ extern "C" int emu_fold_table(int curve, const uint32_t* key, uint32_t n, uint32
   return -1;
 }
 extern "C" int emu_wnaf(const uint32_t* k5, int w, int8_t* out200) { return pc::wnaf_digits(k5, w, out200); }
+
+// The bucket sort alone (sort_entries_atomic, stepped), for tests/test_msm_sort_cpu.py: the geometry from msm_make_geom with the per-call
+// fields as MsmPlan::part_body sets them.  offsets: NB + 1 words; entries: n * Wd words.
+template <class C>
+static int sort_atomic(size_t n, uint32_t c, uint32_t tbl_stride, uint32_t m_sub, uint32_t glv, uint32_t from_mont, uint32_t base_off,
+                       const uint32_t* scalars, uint32_t* offsets, uint32_t* entries) {
+  if (n == 0 || (m_sub && n % m_sub) || ((glv || m_sub) && !tbl_stride)) return -1;
+  CpuStepBackend be;
+  pc::MsmGeom g = pc::msm_make_geom(C::FrP::BITS, n, c, tbl_stride != 0, glv != 0, m_sub ? (uint32_t)(n / m_sub) : 0u, tbl_stride, 0u, 8u, 8u);
+  g.base_off = base_off; g.from_mont = from_mont; g.m_sub = m_sub;
+  std::vector<uint32_t> hist((size_t)g.NB + 1), cursor((size_t)g.NB + 1);
+  pc::sort_entries_atomic<C>(be, g, scalars, hist.data(), offsets, cursor.data(), entries);
+  return 0;
+}
+extern "C" int emu_sort_atomic(int curve, size_t n, uint32_t c, uint32_t tbl_stride, uint32_t m_sub, uint32_t glv, uint32_t from_mont,
+                               uint32_t base_off, const uint32_t* scalars, uint32_t* offsets, uint32_t* entries) {
+  switch (curve) {
+    case 0: return sort_atomic<pc_curve_bls12_381>(n, c, tbl_stride, m_sub, glv, from_mont, base_off, scalars, offsets, entries);
+    case 1: return sort_atomic<pc_curve_bn254>(n, c, tbl_stride, m_sub, glv, from_mont, base_off, scalars, offsets, entries);
+    case 2: return sort_atomic<pc_curve_pallas>(n, c, tbl_stride, m_sub, glv, from_mont, base_off, scalars, offsets, entries);
+    case 3: return sort_atomic<pc_curve_bls12_377>(n, c, tbl_stride, m_sub, glv, from_mont, base_off, scalars, offsets, entries);
+  }
+  return -1;
+}
