@@ -5,7 +5,8 @@ scalar field, the ABI glue, the hash-only kernels); objects are cached under csr
 rebuilt when any source or header is newer.
 
 A second target, tests/hip/libpc_probe.so, is test infrastructure: the field and curve primitives of csrc/ one
-per lane (tests/hip/probe_bodies.hpp, probe_te_bodies.hpp), for tests/test_device_primitives_gpu.py and its siblings.  It has its own object cache
+per lane (tests/hip/probe_bodies.hpp, probe_te_bodies.hpp), for tests/test_device_primitives_gpu.py and its siblings, and two stages of
+the MSM on their own: the bucket sort (probe_sort.hip) and the bucket reduction, level by level (probe_reduce.hip).  It has its own object cache
 (tests/hip/_obj) and staleness check (its sources and the csrc headers); the product library does not contain it."""
 import concurrent.futures
 import os
@@ -33,7 +34,7 @@ PROBE_UNITS = ([("probe_field.hip", k) for k in range(3)] + [("probe_curve.hip",
                [("probe_halfadd.hip", k) for k in range(3)] + [("probe_fq30.hip", None), ("probe_chain30.hip", None)] +
                [("probe_field_bls12_377.hip", None), ("probe_curve_bls12_377.hip", None)] +
                [("probe_field_te.hip", None), ("probe_te.hip", None), ("probe_te_setup.hip", None)] +
-               [("probe_sort.hip", None)])
+               [("probe_sort.hip", None), ("probe_reduce.hip", None)])
 # a unit whose source this tree's tests/hip does not have is left out: a tests/ tree from before the unit was added still builds its
 # probe, and a test that needs the unit fails at its missing entry point
 PROBE_UNITS = [u for u in PROBE_UNITS if os.path.exists(os.path.join(PROBE_DIR, u[0]))]

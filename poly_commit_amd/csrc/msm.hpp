@@ -892,6 +892,55 @@ inline MsmGeom msm_make_geom(uint32_t scalar_bits, size_t n, uint32_t c, bool tb
   return g;
 }
 
+// The reduction-level plan of a call of n pairs with geometry g (MsmPlan::plan_geometry; the test-only reduction probe takes its
+// plans here too): per level the group size K, the elements per bucket set after it (m), the kind (0 serial, 1 one lane per point,
+// 2 two lanes per point) and the number of arrays behind its S array; arr_exp is the log2 weight of every array behind S at the
+// last level.  cfg: K0 / tbl_K0 / K1 already floored to powers of two (MsmPlan's constructor).
+struct MsmLevels {
+  uint32_t n_levels = 0; uint32_t K[32], m[32], mode[32], narr[32];
+  std::vector<uint32_t> arr_exp;
+};
+inline MsmLevels msm_plan_levels(const MsmConfig& cfg, const MsmGeom& g, size_t n, bool tbl) {
+  MsmLevels lv;
+  uint32_t m = g.nb_win;
+  uint32_t kbits = 0;
+  while (m > 1) {
+    // wide levels are throughput-bound: short serial chains (K0).  Once a level holds few enough
+    // points the chain length is all that matters: workgroup-cooperative "bits" levels (K1).
+    uint32_t K;
+    // points this level reads: groups x K x arrays (its weighted array and the older plain ones)
+    const size_t level_pts = (size_t)n * g.Wd <= cfg.coop2_max_entries ? (size_t)g.W * m * (1 + (lv.n_levels ? lv.narr[lv.n_levels - 1] : 0))
+                                                                         : (size_t)-1;      // (no two-lane levels in large MSMs)
+    if ((size_t)g.W * m > cfg.coop_max_points) K = tbl ? cfg.tbl_K0 : cfg.K0;
+    else {
+      // the remaining log2(m) bits are split evenly over the fewest cooperative levels of at most log2(K1) bits each:
+      // the chain is one addition per bit, so 19 bits cost 7 + 6 + 6 dependent additions, not 8 + 8 + a serial tail
+      uint32_t rem = 0; while ((1u << rem) < m) rem++;
+      uint32_t lg1 = 0; while ((1u << lg1) < cfg.K1) lg1++;
+      if (level_pts <= cfg.coop2_max_points && lg1 > 7) lg1 = 7;      // two lanes per point: groups of at most 128
+      const uint32_t nl = (rem + lg1 - 1) / lg1;
+      K = 1u << ((rem + nl - 1) / nl);
+    }
+    if (K > m) K = m;
+    uint32_t lgK = 0; while ((1u << lgK) < K) lgK++;
+    const bool bits = K >= 16;
+    const uint32_t woff = lv.n_levels == 0 ? 1u : 0u;
+    const uint32_t nw = bits ? lgK + woff : 1u;
+    lv.K[lv.n_levels] = K; m /= K; lv.m[lv.n_levels] = m;   // m = elements per window AFTER this level
+    lv.mode[lv.n_levels] = !bits ? 0u : (K <= 128 && level_pts <= cfg.coop2_max_points) ? 2u : 1u;
+    lv.narr[lv.n_levels] = nw + (lv.n_levels ? lv.narr[lv.n_levels - 1] : 0);
+    // weights of the new arrays (as powers of two), then the older arrays keep theirs
+    std::vector<uint32_t> e;
+    if (bits) { for (uint32_t b = 0; b < lgK; b++) e.push_back(kbits + b); if (woff) e.push_back(kbits); }
+    else e.push_back(kbits);
+    e.insert(e.end(), lv.arr_exp.begin(), lv.arr_exp.end());
+    lv.arr_exp.swap(e);
+    kbits += lgK;
+    lv.n_levels++;
+  }
+  return lv;
+}
+
 template <class C, class Backend>
 class MsmPlan {
  public:
@@ -1229,42 +1278,10 @@ class MsmPlan {
     const bool tbl = subs_ || (cfg_.tbl && cfg_.tbl_c && n >= cfg_.tbl_min_n);
     uint32_t c = tbl ? cfg_.tbl_c : cfg_.c ? cfg_.c : msm_choose_c(n, FrP::BITS);
     g_ = msm_make_geom(FrP::BITS, n, c, tbl, tbl && cfg_.tbl_glv, subs_, cfg_.tbl_stride, tbl ? cfg_.tbl_pt_stride : (uint32_t)AW, cfg_.T2, cfg_.T2b);
-    uint32_t m = g_.nb_win; n_levels_ = 0;
-    uint32_t kbits = 0; arr_exp_.clear();
-    while (m > 1) {
-      // wide levels are throughput-bound: short serial chains (K0).  Once a level holds few enough
-      // points the chain length is all that matters: workgroup-cooperative "bits" levels (K1).
-      uint32_t K;
-      // points this level reads: groups x K x arrays (its weighted array and the older plain ones)
-      const size_t level_pts = (size_t)n * g_.Wd <= cfg_.coop2_max_entries ? (size_t)g_.W * m * (1 + (n_levels_ ? lvl_narr_[n_levels_ - 1] : 0))
-                                                                           : (size_t)-1;      // (no two-lane levels in large MSMs)
-      if ((size_t)g_.W * m > cfg_.coop_max_points) K = tbl ? cfg_.tbl_K0 : cfg_.K0;
-      else {
-        // the remaining log2(m) bits are split evenly over the fewest cooperative levels of at most log2(K1) bits each:
-        // the chain is one addition per bit, so 19 bits cost 7 + 6 + 6 dependent additions, not 8 + 8 + a serial tail
-        uint32_t rem = 0; while ((1u << rem) < m) rem++;
-        uint32_t lg1 = 0; while ((1u << lg1) < cfg_.K1) lg1++;
-        if (level_pts <= cfg_.coop2_max_points && lg1 > 7) lg1 = 7;      // two lanes per point: groups of at most 128
-        const uint32_t nl = (rem + lg1 - 1) / lg1;
-        K = 1u << ((rem + nl - 1) / nl);
-      }
-      if (K > m) K = m;
-      uint32_t lgK = 0; while ((1u << lgK) < K) lgK++;
-      const bool bits = K >= 16;
-      const uint32_t woff = n_levels_ == 0 ? 1u : 0u;
-      const uint32_t nw = bits ? lgK + woff : 1u;
-      lvl_K_[n_levels_] = K; m /= K; lvl_m_[n_levels_] = m;   // m = elements per window AFTER this level
-      lvl_bits_[n_levels_] = !bits ? 0u : (K <= 128 && level_pts <= cfg_.coop2_max_points) ? 2u : 1u;
-      lvl_narr_[n_levels_] = nw + (n_levels_ ? lvl_narr_[n_levels_ - 1] : 0);
-      // weights of the new arrays (as powers of two), then the older arrays keep theirs
-      std::vector<uint32_t> e;
-      if (bits) { for (uint32_t b = 0; b < lgK; b++) e.push_back(kbits + b); if (woff) e.push_back(kbits); }
-      else e.push_back(kbits);
-      e.insert(e.end(), arr_exp_.begin(), arr_exp_.end());
-      arr_exp_.swap(e);
-      kbits += lgK;
-      n_levels_++;
-    }
+    const MsmLevels lv = msm_plan_levels(cfg_, g_, n, tbl);
+    n_levels_ = lv.n_levels;
+    for (uint32_t l = 0; l < lv.n_levels; l++) { lvl_K_[l] = lv.K[l]; lvl_m_[l] = lv.m[l]; lvl_bits_[l] = lv.mode[l]; lvl_narr_[l] = lv.narr[l]; }
+    arr_exp_ = lv.arr_exp;
   }
 
   // Horner over (level, window) on the host.  P_j[w] has weight 2^(c*w + k_0 + ... + k_{j-1}).
