@@ -853,6 +853,27 @@ int pc_hip_te_sample_generators(pc_ctx* ctx, pc_te_curve curve, const void* prot
  * count == 0 or beyond the key: PC_ERR_INVALID_ARG. */
 int pc_hip_te_srs_prefix(pc_ctx* ctx, const pc_te_srs* src, size_t count, pc_te_srs** out);
 
+/* ---- setup on the short Weierstrass curves: InnerProductArgPC (ipa_pc/mod.rs:302-325, :344-400) and HyraxPC (hyrax/mod.rs:119-168) ----
+ * sample_generators with D = Blake2s256 over a curve of pc_curve: generators [first_index, first_index + count) as a NEW resident key
+ * (the caller frees it with pc_hip_srs_free), made on the device, one lane per index -- generator i is h * from_random_bytes(D(name ||
+ * le64(i))), or while that is None, for j = 0, 1, ..., h * from_random_bytes(D(name || le64(i) || le64(j))), h the curve's cofactor
+ * (mul_by_cofactor_to_group: 1 for BN254 and Pallas, 126 / 125 bits for G1 of BLS12-381 / BLS12-377); then normalize_batch.  The loop of
+ * hyrax/mod.rs:119-168 is the same one.  InnerProductArgPC::setup (:344-366) is this call with "PC-DL-2020", first_index = 0 and
+ * count = max_degree + 3; HyraxPC::setup with "Hyrax protocol" and count = 2^(n/2) + 1.  protocol_name: name_len <= 48 bytes on the host
+ * (may be null at 0).  out_digests_host (optional, count entries): the digests index first_index + k consumed (1: the first one was
+ * accepted).  BN254's from_random_bytes can return the identity (flag bits of the digest's last byte): it is then the generator, stored
+ * as the all-zero point.  short_weierstrass::Affine::from_random_bytes -- the place of the two flag bits per base field, and which of
+ * the two roots a flag names -- is restated from ark-ec / ark-ff 0.5 (csrc/sw_setup.hpp) and NOT confirmed against the crates; either
+ * root gives a valid key.  count == 0, name_len > 48, first_index + count beyond 64 bits, an unknown curve id: PC_ERR_INVALID_ARG;
+ * count >= 2^31: PC_ERR_TOO_LARGE.  A lane's retry loop is capped at 256 digests (a rejection has probability 0.5 to 0.81):
+ * PC_ERR_INTERNAL, and no key, if one ever hits the cap. */
+int pc_hip_sample_generators(pc_ctx* ctx, pc_curve curve, const void* protocol_name, size_t name_len, uint64_t first_index, size_t count,
+                             uint32_t* out_digests_host, pc_srs** out);
+/* trim's comm_key[0..count) (ipa_pc/mod.rs:384): a NEW resident key of the first `count` points of src, a device copy (the caller
+ * frees it); src is untouched.  The new key carries no window table and no fold table.  count == 0 or beyond the key:
+ * PC_ERR_INVALID_ARG. */
+int pc_hip_srs_prefix(pc_ctx* ctx, const pc_srs* src, size_t count, pc_srs** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,8 @@ def load_library():
     lib.pc_hip_te_point_mul.argtypes = [ip, vp, vp, vp]
     lib.pc_hip_te_sample_generators.argtypes = [vp, ip, vp, sz, C.c_uint64, sz, C.POINTER(C.c_uint32), C.POINTER(vp)]
     lib.pc_hip_te_srs_prefix.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    lib.pc_hip_sample_generators.argtypes = [vp, ip, vp, sz, C.c_uint64, sz, C.POINTER(C.c_uint32), C.POINTER(vp)]
+    lib.pc_hip_srs_prefix.argtypes = [vp, vp, sz, C.POINTER(vp)]
     lib.pc_hip_ml_fold.argtypes = [vp, ip, vp, sz, vp, vp, vp]
     lib.pc_hip_ml_open.argtypes = [vp, vp, vp, ip, C.c_uint, vp, vp, C.POINTER(ip)]
     lib.pc_hip_ml_eq_evals.argtypes = [vp, ip, vp, C.c_uint, vp]
@@ -601,6 +603,18 @@ class Context:
         self.check(self.lib.pc_hip_te_sample_generators(self.h, TE_CURVES[curve], name, len(name), first_index, count,
                                                         digests.ctypes.data_as(C.POINTER(C.c_uint32)) if want_digests else None, C.byref(h)))
         key = TeSrs._adopt(self, curve, h, count)
+        return (key, digests[:count]) if want_digests else key
+
+    def sample_generators(self, curve, protocol_name, first_index, count, want_digests=False):
+        """sample_generators over a short Weierstrass curve on the device (pc_hip_sample_generators; ipa_pc/mod.rs:302-325,
+        hyrax/mod.rs:119-168): generators [first_index, first_index + count) of the byte string protocol_name (at most 48 bytes) as a
+        new resident Srs; with want_digests also the uint32 array of the digests every index consumed (1: the first one was accepted)."""
+        name = bytes(protocol_name)
+        digests = np.zeros(max(count, 1), dtype=np.uint32) if want_digests else None
+        h = C.c_void_p()
+        self.check(self.lib.pc_hip_sample_generators(self.h, CURVES[curve], name, len(name), first_index, count,
+                                                     digests.ctypes.data_as(C.POINTER(C.c_uint32)) if want_digests else None, C.byref(h)))
+        key = Srs._adopt(self, curve, h, count)
         return (key, digests[:count]) if want_digests else key
 
     def te_fr_powers(self, curve, z_mont, n, out_dev):
@@ -1037,6 +1051,13 @@ class Srs:
         out = Srs.__new__(Srs)
         out.ctx, out.curve, out.h, out.n = self.ctx, self.curve, h, n_half
         return out
+
+    def prefix(self, count):
+        """A new resident key of the first `count` points, a device copy; this key is untouched (pc_hip_srs_prefix): trim's
+        comm_key[0..count) (ipa_pc/mod.rs:384).  The new key has no window or fold table."""
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.pc_hip_srs_prefix(self.ctx.h, self.h, count, C.byref(h)))
+        return Srs._adopt(self.ctx, self.curve, h, count)
 
     def device_ptr(self):
         """Address of the resident packed point array (pc_hip_srs_device_ptr)."""

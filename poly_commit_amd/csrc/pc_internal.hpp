@@ -18,6 +18,8 @@
 //                      by abi_g2.hip and abi_te.hip alone, each instantiating it for its own group
 //   abi_te.hpp         what the three twisted Edwards units share: the group's names and sizes, the id check, the normalisation tail
 //   abi_te_setup.hip   sample_generators and the prefix of a twisted Edwards key (te_setup.hpp)
+//   abi_setup.hip      sample_generators and the prefix of a key over the short Weierstrass curves (sw_setup.hpp): it instantiates the
+//                      sampling kernels of all four curves itself
 //   abi_te_ipa.hip     the FrVecOps table of ed_on_bls12_381's scalar field (no NTT, no FieldOps entry) and the opening as one call
 //   fixed_base.hpp     the group-generic launch sequences (fixed-base batch multiplication, pair sums): one copy, instantiated for
 //                      G1 by the curve units and for G2 by abi_g2.hip

@@ -45,6 +45,8 @@ GROUPS = [
       "pc_hip_te_srs_in_subgroup", "pc_hip_te_ipa_open_rounds"]),
     ("InnerProductArgPC::setup and trim over ed_on_bls12_381 on the device (ipa_pc/mod.rs:302-325, 344-400): sample_generators -- Blake2s, from_random_bytes with its square root, the cofactor, normalize_batch -- as a new resident key, and trim's prefix of it",
      ["pc_hip_te_sample_generators", "pc_hip_te_srs_prefix"]),
+    ("InnerProductArgPC::setup and trim (ipa_pc/mod.rs:302-325, 344-400) and HyraxPC::setup (hyrax/mod.rs:119-168) over the short Weierstrass curves on the device: sample_generators -- Blake2s, short_weierstrass from_random_bytes with its square root, mul_by_cofactor_to_group, normalize_batch -- as a new resident key, and trim's prefix of it",
+     ["pc_hip_sample_generators", "pc_hip_srs_prefix"]),
     ("HyraxPC over ed_on_bls12_381, the reference's Hyrax381 (hyrax/tests.rs:6,20-21): commit's Pedersen commitment per matrix row as one many-MSM pass over a window table of the key (hyrax/mod.rs:86-93, 233-242), and the vectors of open over the 252-bit scalar field -- row_mul (:347, :391) and the inner product (:356)",
      ["pc_hip_te_msm_many", "pc_hip_te_fr_lincomb", "pc_hip_te_fr_dot"]),
     ("one committer key over the GPUs of a node, one process",
