@@ -70,7 +70,8 @@ void pc_hip_srs_free(pc_srs* srs);
  * (ipa_pc/data_structures.rs:17-36).  At most max_points points (0 = all) are decoded ON THE DEVICE (compressed points:
  * y = (x^3 + b)^((p+1)/4) for BLS12-381 and BN254) into a resident SRS; *out_bytes_consumed = 8 + len * point size, where
  * the next field of the structure starts.  Pallas (p = 1 mod 2^32) and BLS12-377 (p = 1 mod 2^46) take their square roots by Tonelli-Shanks.  Every decoded point is checked to be on the curve (PC_ERR_INVALID_ARG
- * otherwise); the subgroup check of Validate::Yes is the verifier-side `check()` and is not repeated here.
+ * otherwise); the subgroup check of Validate::Yes is not made by this call: pc_hip_srs_load_serialized_ex (below) makes it on request,
+ * pc_hip_srs_check on a key that is already resident.
  * Point encodings: host/transcript.hpp / csrc/serialize.hpp (ark-ec's generic short-Weierstrass flags; the zcash
  * encoding for BLS12-381; BLS12-377 takes the generic form: 48 / 96 bytes, flags in the top bits of the last byte). */
 int pc_hip_srs_load_serialized(pc_ctx* ctx, pc_curve curve, const void* bytes, size_t n_bytes, int compressed,
@@ -113,7 +114,9 @@ int pc_hip_srs_precompute(pc_ctx* ctx, pc_srs* srs, unsigned window_bits, size_t
 #define PC_HIP_TABLE_GLV_IF_LARGE 4
 int pc_hip_srs_precompute_ex(pc_ctx* ctx, pc_srs* srs, unsigned window_bits, size_t min_pairs, unsigned flags);
 size_t pc_hip_srs_len(const pc_srs* srs);
-/* Device pointer of the packed (x||y) resident bases, for callers that build on it. */
+/* Device pointer of the packed (x||y) resident bases, for callers that build on it.  The pointer is writable and the library does not
+ * see writes made through it: what pc_hip_srs_in_subgroup knows about the key (below) is NOT reset by them -- a caller that rewrites
+ * points this way validates with pc_hip_srs_check, which always looks at the points. */
 void* pc_hip_srs_device_ptr(const pc_srs* srs);
 
 /* Variable-base MSM:  out = sum_{i<n} scalars[i] * bases[base_offset + i].
@@ -870,9 +873,48 @@ int pc_hip_te_srs_prefix(pc_ctx* ctx, const pc_te_srs* src, size_t count, pc_te_
 int pc_hip_sample_generators(pc_ctx* ctx, pc_curve curve, const void* protocol_name, size_t name_len, uint64_t first_index, size_t count,
                              uint32_t* out_digests_host, pc_srs** out);
 /* trim's comm_key[0..count) (ipa_pc/mod.rs:384): a NEW resident key of the first `count` points of src, a device copy (the caller
- * frees it); src is untouched.  The new key carries no window table and no fold table.  count == 0 or beyond the key:
- * PC_ERR_INVALID_ARG. */
+ * frees it); src is untouched.  The new key carries no window table and no fold table; a known subgroup membership of 1
+ * (pc_hip_srs_in_subgroup) carries over.  count == 0 or beyond the key: PC_ERR_INVALID_ARG. */
 int pc_hip_srs_prefix(pc_ctx* ctx, const pc_srs* src, size_t count, pc_srs** out);
+
+/* ---- validation of resident keys: the check() of Validate::Yes -------------------------------------------------------------------
+ * UniversalParams::deserialize_with_mode(.., Validate::Yes) ends in result.check() (poly-commit/src/kzg10/data_structures.rs:41-49,
+ * :106-108); powers_of_g.check() is, per point, is_on_curve() && is_in_correct_subgroup_assuming_on_curve(), and an IPA or Hyrax key
+ * (a Vec<G>) deserialized with validation does the same.  On the device, one lane per point (csrc/validate.hpp):
+ *   PC_HIP_CHECK_ON_CURVE   the all-zero encoding of infinity, or both coordinates below the modulus (Montgomery residues, as the key
+ *                           holds them) and y^2 = x^3 + b
+ *   PC_HIP_CHECK_SUBGROUP   r * P is the point at infinity, r the scalar field's modulus.  It assumes an on-curve point, as arkworks'
+ *                           name says; with both bits a point off the curve fails once and no ladder runs on it.  BN254 and Pallas have
+ *                           cofactor 1: every point passes without a launch (ark-ec's cofactor_is_one()).  BLS12-381 and BLS12-377 take
+ *                           the test ark-bls12-381 / ark-bls12-377 override the method with, phi(P) = -[x^2] P (eprint 2021/1130
+ *                           section 6); PC_HIP_SUBGROUP_LADDER=1 in the environment forces the plain ladder by r,
+ *                           which is the definition: both give the same answers.
+ * pc_hip_srs_check is a query over points [offset, offset + count): PC_OK with *out_bad = how many points failed and *out_first_bad
+ * (may be NULL) = the lowest failing index relative to `offset`, undefined when *out_bad == 0; both are made on the device (a counter
+ * and an atomic minimum).  out_ok_host: `count` bytes, 1 for a point that passed, copied out only when not NULL.  count == 0: PC_OK,
+ * *out_bad = 0.  A range beyond the key, what == 0 or unknown bits, a key of another context: PC_ERR_INVALID_ARG. */
+#define PC_HIP_CHECK_ON_CURVE 1u
+#define PC_HIP_CHECK_SUBGROUP 2u
+int pc_hip_srs_check(pc_ctx* ctx, const pc_srs* srs, size_t offset, size_t count, unsigned what, size_t* out_bad, size_t* out_first_bad,
+                     uint8_t* out_ok_host);
+/* *out = 1 if every point of the key passes PC_HIP_CHECK_SUBGROUP, else 0; asked once and kept on the key, as pc_hip_te_srs_in_subgroup
+ * does.  The answer is known without a launch where it provably holds: a key made by pc_hip_sample_generators (the cofactor was cleared)
+ * and a key loaded with pc_hip_srs_load_serialized_ex(.., PC_HIP_CHECK_SUBGROUP) start at 1; pc_hip_srs_prefix, pc_hip_ec_fold,
+ * pc_hip_ec_fold_from and pc_hip_ec_fold2_from keep a 1 (sums of multiples of subgroup points stay in the subgroup); every other call
+ * OF THIS LIBRARY that rewrites the points forgets the answer.  Writes a caller makes itself through pc_hip_srs_device_ptr are not seen:
+ * a cached answer, and the 1 of a generated or validated key, survive them -- pc_hip_srs_check is the call that always reads the points.
+ * pc_hip_srs_upload never validates by itself. */
+int pc_hip_srs_in_subgroup(pc_ctx* ctx, pc_srs* srs, int* out);
+/* pc_hip_srs_load_serialized with the validation the caller names: validate = 0 is that call exactly (Validate::No plus the curve
+ * equation, which the decoder always tests); PC_HIP_CHECK_ON_CURVE | PC_HIP_CHECK_SUBGROUP is Validate::Yes
+ * (kzg10/data_structures.rs:106-108).  A decoded key with a point outside the subgroup gives PC_ERR_INVALID_ARG and no key;
+ * pc_hip_last_error names how many points failed and the first index.  Unknown bits: PC_ERR_INVALID_ARG. */
+int pc_hip_srs_load_serialized_ex(pc_ctx* ctx, pc_curve curve, const void* bytes, size_t n_bytes, int compressed, size_t max_points,
+                                  unsigned validate, pc_srs** out, size_t* out_points, size_t* out_bytes_consumed);
+/* pc_hip_srs_check for a G2 key (BLS12-381 only; any other id: PC_ERR_INVALID_ARG, as for the other pc_hip_g2_* calls): the twist
+ * y^2 = x^3 + 4 (1 + u) with every coefficient below the modulus, and the plain ladder by r (no psi shortcut: G2 keys are short). */
+int pc_hip_g2_srs_check(pc_ctx* ctx, const pc_g2_srs* srs, size_t offset, size_t count, unsigned what, size_t* out_bad,
+                        size_t* out_first_bad, uint8_t* out_ok_host);
 
 #ifdef __cplusplus
 }

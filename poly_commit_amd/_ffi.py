@@ -179,6 +179,10 @@ def load_library():
     lib.pc_hip_te_srs_prefix.argtypes = [vp, vp, sz, C.POINTER(vp)]
     lib.pc_hip_sample_generators.argtypes = [vp, ip, vp, sz, C.c_uint64, sz, C.POINTER(C.c_uint32), C.POINTER(vp)]
     lib.pc_hip_srs_prefix.argtypes = [vp, vp, sz, C.POINTER(vp)]
+    lib.pc_hip_srs_check.argtypes = [vp, vp, sz, sz, C.c_uint, C.POINTER(sz), C.POINTER(sz), vp]
+    lib.pc_hip_srs_in_subgroup.argtypes = [vp, vp, C.POINTER(ip)]
+    lib.pc_hip_srs_load_serialized_ex.argtypes = [vp, ip, vp, sz, ip, sz, C.c_uint, C.POINTER(vp), C.POINTER(sz), C.POINTER(sz)]
+    lib.pc_hip_g2_srs_check.argtypes = [vp, vp, sz, sz, C.c_uint, C.POINTER(sz), C.POINTER(sz), vp]
     lib.pc_hip_ml_fold.argtypes = [vp, ip, vp, sz, vp, vp, vp]
     lib.pc_hip_ml_open.argtypes = [vp, vp, vp, ip, C.c_uint, vp, vp, C.POINTER(ip)]
     lib.pc_hip_ml_eq_evals.argtypes = [vp, ip, vp, C.c_uint, vp]
@@ -719,16 +723,36 @@ class Context:
     def trim(self):
         self.check(self.lib.pc_hip_ctx_trim(self.h))
 
-    def load_serialized_srs(self, curve, data, compressed, max_points=0):
+    def load_serialized_srs(self, curve, data, compressed, max_points=0, validate=None):
         """Resident SRS from the ark-serialize bytes of a Vec<G1Affine> (the head of kzg10::UniversalParams):
-        returns (Srs, bytes_consumed)."""
+        returns (Srs, bytes_consumed).  validate: None is pc_hip_srs_load_serialized (Validate::No plus the curve equation); an integer
+        of CHECK_ON_CURVE | CHECK_SUBGROUP goes to pc_hip_srs_load_serialized_ex, and True is both bits: Validate::Yes."""
         h, npts, used = C.c_void_p(), C.c_size_t(), C.c_size_t()
         buf = (C.c_char * len(data)).from_buffer_copy(data)
-        self.check(self.lib.pc_hip_srs_load_serialized(self.h, CURVES[curve], buf, len(data), 1 if compressed else 0, max_points,
-                                                       C.byref(h), C.byref(npts), C.byref(used)))
+        if validate is None:
+            self.check(self.lib.pc_hip_srs_load_serialized(self.h, CURVES[curve], buf, len(data), 1 if compressed else 0, max_points,
+                                                           C.byref(h), C.byref(npts), C.byref(used)))
+        else:
+            what = (CHECK_ON_CURVE | CHECK_SUBGROUP) if validate is True else int(validate)
+            self.check(self.lib.pc_hip_srs_load_serialized_ex(self.h, CURVES[curve], buf, len(data), 1 if compressed else 0, max_points,
+                                                              what, C.byref(h), C.byref(npts), C.byref(used)))
         srs = Srs.__new__(Srs)
         srs.ctx, srs.curve, srs.h, srs.n = self, curve, h, npts.value
         return srs, used.value
+
+
+CHECK_ON_CURVE, CHECK_SUBGROUP = 1, 2      # PC_HIP_CHECK_ON_CURVE, PC_HIP_CHECK_SUBGROUP
+
+
+def _key_check(ctx, fn, handle, n, offset, count, on_curve, subgroup, want_flags):
+    """pc_hip_srs_check / pc_hip_g2_srs_check -> (bad, first_bad or None[, flags])"""
+    count = n - offset if count is None else count
+    what = (CHECK_ON_CURVE if on_curve else 0) | (CHECK_SUBGROUP if subgroup else 0)
+    bad, first = C.c_size_t(), C.c_size_t()
+    flags = np.zeros(count, dtype=np.uint8) if want_flags else None
+    ctx.check(fn(ctx.h, handle, offset, count, what, C.byref(bad), C.byref(first), C.c_void_p(flags.ctypes.data) if want_flags else None))
+    out = (bad.value, first.value if bad.value else None)
+    return out + (flags,) if want_flags else out
 
 
 class BrakedownCode:
@@ -1059,6 +1083,18 @@ class Srs:
         self.ctx.check(self.ctx.lib.pc_hip_srs_prefix(self.ctx.h, self.h, count, C.byref(h)))
         return Srs._adopt(self.ctx, self.curve, h, count)
 
+    def check(self, offset=0, count=None, on_curve=True, subgroup=True, want_flags=False):
+        """The check() of Validate::Yes over points [offset, offset + count) (pc_hip_srs_check): returns (bad, first_bad) -- how many
+        points failed and the lowest failing index relative to offset (None when none failed) -- and with want_flags a third item,
+        one byte per point, 1 for a point that passed."""
+        return _key_check(self.ctx, self.ctx.lib.pc_hip_srs_check, self.h, self.n, offset, count, on_curve, subgroup, want_flags)
+
+    def in_subgroup(self):
+        """True if every point of the key lies in the prime-order subgroup (pc_hip_srs_in_subgroup; cached on the key)."""
+        out = C.c_int(-1)
+        self.ctx.check(self.ctx.lib.pc_hip_srs_in_subgroup(self.ctx.h, self.h, C.byref(out)))
+        return bool(out.value)
+
     def device_ptr(self):
         """Address of the resident packed point array (pc_hip_srs_device_ptr)."""
         return int(self.ctx.lib.pc_hip_srs_device_ptr(self.h))
@@ -1134,6 +1170,10 @@ class G2Srs:
         out = np.zeros((count, 4 * FQ_BYTES[self.curve]), dtype=np.uint8)
         self.ctx.check(self.ctx.lib.pc_hip_g2_srs_read(self.ctx.h, self.h, offset, count, C.c_void_p(out.ctypes.data)))
         return out
+
+    def check(self, offset=0, count=None, on_curve=True, subgroup=True, want_flags=False):
+        """Srs.check for a G2 key (pc_hip_g2_srs_check): the twist's equation and the plain ladder by r."""
+        return _key_check(self.ctx, self.ctx.lib.pc_hip_g2_srs_check, self.h, self.n, offset, count, on_curve, subgroup, want_flags)
 
     def pair_sums_into(self, out_key, off, count, out_off):
         """out_key[out_off + b] = self[off + 2b] + self[off + 2b + 1], b < count (pc_hip_g2_srs_pair_sums)."""

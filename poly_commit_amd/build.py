@@ -6,7 +6,8 @@ rebuilt when any source or header is newer.
 
 A second target, tests/hip/libpc_probe.so, is test infrastructure: the field and curve primitives of csrc/ one
 per lane (tests/hip/probe_bodies.hpp, probe_te_bodies.hpp), for tests/test_device_primitives_gpu.py and its siblings, and two stages of
-the MSM on their own: the bucket sort (probe_sort.hip) and the bucket reduction, level by level (probe_reduce.hip).  It has its own object cache
+the MSM on their own: the bucket sort (probe_sort.hip) and the bucket reduction, level by level (probe_reduce.hip); probe_validate.hip runs the key
+validation bodies (csrc/validate.hpp).  It has its own object cache
 (tests/hip/_obj) and staleness check (its sources and the csrc headers); the product library does not contain it."""
 import concurrent.futures
 import os
@@ -14,7 +15,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["abi_ctx.hip", "abi_srs.hip", "abi_msm.hip", "abi_poly.hip", "abi_ipa.hip", "abi_lincode.hip", "abi_g2.hip", "abi_te.hip", "abi_te_ipa.hip", "abi_te_setup.hip", "abi_setup.hip", "abi_skzg.hip", "abi_pst13.hip", "group.hip", "hash_tu.hip",
+SOURCES = ["abi_ctx.hip", "abi_srs.hip", "abi_msm.hip", "abi_poly.hip", "abi_ipa.hip", "abi_lincode.hip", "abi_g2.hip", "abi_te.hip", "abi_te_ipa.hip", "abi_te_setup.hip", "abi_setup.hip", "abi_skzg.hip", "abi_pst13.hip", "abi_validate.hip", "group.hip", "hash_tu.hip",
            "curve_bls12_381.hip", "curve_bn254.hip", "curve_pallas.hip", "curve_bls12_377.hip",
            "field_bls12_381.hip", "field_bn254.hip", "field_pallas.hip", "field_bls12_377.hip"]
 # PC_HIP_VARIANT=name builds an alternative library libpc_hip_<name>.so (own object cache) from the same sources with
@@ -34,7 +35,7 @@ PROBE_UNITS = ([("probe_field.hip", k) for k in range(3)] + [("probe_curve.hip",
                [("probe_halfadd.hip", k) for k in range(3)] + [("probe_fq30.hip", None), ("probe_chain30.hip", None)] +
                [("probe_field_bls12_377.hip", None), ("probe_curve_bls12_377.hip", None)] +
                [("probe_field_te.hip", None), ("probe_te.hip", None), ("probe_te_setup.hip", None), ("probe_sw_setup.hip", None)] +
-               [("probe_sort.hip", None), ("probe_reduce.hip", None)])
+               [("probe_sort.hip", None), ("probe_reduce.hip", None), ("probe_validate.hip", None)])
 # a unit whose source this tree's tests/hip does not have is left out: a tests/ tree from before the unit was added still builds its
 # probe, and a test that needs the unit fails at its missing entry point
 PROBE_UNITS = [u for u in PROBE_UNITS if os.path.exists(os.path.join(PROBE_DIR, u[0]))]

@@ -42,6 +42,7 @@ int pc_hip_ec_fold(pc_ctx* ctx, pc_srs* srs, size_t n_half, const void* u_host) 
     drop_table(srs);                            // the key changes: its window tables are stale
     drop_many(srs);
     drop_fold_table(srs);
+    if (srs->in_subgroup != 1) srs->in_subgroup = -1;      // a 1 stays (sums of multiples of subgroup points); anything else is forgotten
     pc::curve_ops(srs->curve).ec_fold_to(ctx->be, srs->bases, srs->bases, n_half, (const uint32_t*)u_host, nullptr, 0);
     return (int)PC_OK;
   });

@@ -68,6 +68,7 @@ int pc_hip_sample_generators(pc_ctx* ctx, pc_curve curve, const void* protocol_n
       ctx->last_error = "sample_generators: an index found no point within " + std::to_string(pc::SW_SETUP_MAX_DIGESTS) + " digests";
       return (int)PC_ERR_INTERNAL;
     }
+    k->in_subgroup = 1;  // h * P in a group of order h r
     srs_lane(k, 0);      // the first pipeline now, as pc_hip_srs_upload does: no memory for it surfaces here
     return (int)PC_OK;
   });
@@ -78,6 +79,7 @@ int pc_hip_srs_prefix(pc_ctx* ctx, const pc_srs* src, size_t count, pc_srs** out
   return key_make(ctx, out, [&]() { return key_create(ctx, src->curve, count); }, key_free, [&](pc_srs* k) {
     ctx->be.copy_d2d(k->bases, src->bases, count * (size_t)src->aw * 4);
     ctx->be.sync();
+    if (src->in_subgroup == 1) k->in_subgroup = 1;
     srs_lane(k, 0);
     return (int)PC_OK;
   });

@@ -78,6 +78,7 @@ struct pc_srs : pc_key_base {
   pc_srs* fixed_cache = nullptr; // pc_hip_ipa_open_rounds: the key object of the late rounds' FIXED key (n0 points, its window table, its pipelines), refilled by every opening
   pc_srs* work_out = nullptr;    // the working key currently handed out
   pc::MsmConfig cfg;
+  int in_subgroup = -1;          // pc_hip_srs_in_subgroup's cached answer (-1: not known); whoever rewrites the points resets it
   MsmLane* lanes[PC_MSM_LANES] = {nullptr, nullptr, nullptr};
   int next_lane = 0;
   // pc_hip_msm_many: window table of bases[base_offset .. base_offset + m) and the pipeline sized for B x m
@@ -383,6 +384,7 @@ inline int key_fold_to_working(pc_ctx* ctx, pc_srs* par, size_t count, pc_srs** 
     if (fresh) { dst = key_create(ctx, par->curve, count); if (!dst) return (int)PC_ERR_OOM; }
     else { dst = par->work_cache; par->work_cache = nullptr; drop_table(dst); drop_many(dst); }
     fold(dst);
+    dst->in_subgroup = par->in_subgroup == 1 ? 1 : -1;      // sums of multiples of subgroup points
     if (fresh) for (int i = 0; i < PC_MSM_LANES; i++) srs_lane(dst, i);      // all pipelines now: the next rounds' MSMs find them ready
     return (int)PC_OK;
   });
@@ -421,6 +423,7 @@ inline pc_srs* key_fixed(pc_ctx* ctx, pc_srs* root, const pc_srs* src, size_t n0
       root->fixed_cache = fk;
     }
     ctx->be.copy_d2d(fk->bases, src->bases, n0 * (size_t)root->aw * 4);
+    fk->in_subgroup = src->in_subgroup == 1 ? 1 : -1;
     static const unsigned fixed_c = []() { const char* e = getenv("PC_HIP_IPA_FIXED_C"); int v = e ? atoi(e) : 0; return (unsigned)(v >= 4 && v <= 22 ? v : 0); }();      // measurements: the table's window width
     if (!fk->table) return pc_hip_srs_precompute_ex(ctx, fk, fixed_c, 1, 0);                    // first opening: table, pipelines (full form: the key is small)
     key_drain(fk);
